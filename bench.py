@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- train images/sec of the self-supervised depth/pose training step on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--config c2|c4|c5]
+    python bench.py --gpus N --steps K --warmup W [--config c2|c4|c5] [--dump-outputs DIR] [--full]
     N > 1 works both ways: under an external `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py
     --gpus N ...` (RANK / WORLD_SIZE set), or stand-alone -- then this process starts that launcher itself (one fresh
     child per GPU, before anything here touches the GPU) and relays rank 0's JSON line.
@@ -12,9 +12,11 @@ L1 + SSIM + smoothness loss in the gfx950 HIP kernels, backward, [RCCL all-reduc
 One "image" = one 5-frame 128x416 snippet (BASELINE.json).  Workload at N=1 = BASELINE.json configs[1]
 (batch 8 per GPU); N>1 keeps 8 snippets per GPU (weak scaling, configs[2]).
 
-Rank 0 prints ONE JSON line; `roofline` prices the warp+photometric HIP kernel of the largest scale against the
-HBM peak with HIP events on the launch stream; `cpu_baseline` times the oracle / CPU port of the same step on the
-host cores (N=1 only).  Nothing here reads /root/reference.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the
+line; everything else it can measure runs only with --full: the "did it train" check over four more steps,
+`all_reduce_us`, `sustained`, `epoch_loop`, `host_fed`, `roofline` (the warp+photometric HIP kernel of the largest
+scale priced against the HBM peak with HIP events on the launch stream) and `cpu_baseline` (the oracle / CPU port of
+the same step timed on the host cores, N=1 only).  Nothing here reads the reference project.
 """
 import argparse
 import json
@@ -63,12 +65,17 @@ def parse():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=20.0)
     ap.add_argument("--data", default="resident", choices=["resident", "tfrecord"],
-                    help="tfrecord: ALSO write a synthetic shard set with the repo's TFRecord writer and train from it through the "
+                    help="tfrecord (with --full): ALSO write a synthetic shard set with the repo's TFRecord writer and train from it through the "
                          "prefetching reader (`host_fed`: reader alone, and the step fed from the host; never `value`)")
     ap.add_argument("--no-host-fed", action="store_true",
                     help="skip the `host_fed` leg (TFRecord shards written, read back through the prefetching reader, trained on)")
     ap.add_argument("--sustained-seconds", type=float, default=6.0,
                     help="back-to-back steps after the timed region, reported separately (`sustained`); 0 disables")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beyond the headline figure: the loss-decrease check, all_reduce_us, sustained, "
+                         "epoch_loop, host_fed, roofline and cpu_baseline (the --no-* / --sustained-seconds options trim them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (predictions, total loss, loss by type) as DIR/<name>.npy")
     args = ap.parse_args()
     if args.config == "c4":
         args.height, args.width, args.batch = 256, 832, 4
@@ -224,6 +231,47 @@ def cpu_baseline(args, seconds):
     return cpu_step.timed_baseline(height=args.height, width=args.width, batch=4, budget_s=seconds)
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out, path):
+    """--dump-outputs: what one training step hands its caller, (predictions, total loss, loss by type), as
+    <path>/<name>.npy, one file per tensor (`preds.depth_ms.0`, `loss`, `loss_by_type.SSIM`, ...), float64 tensors as
+    float64 and all others as float32.  Above DUMP_LIMIT_BYTES in all, the arrays that do not fit an even split of what is
+    left of the budget (smallest first) keep a sample of their elements, drawn with a fixed seed and flattened: runs with
+    the same arguments keep the same positions, and small arrays (losses, poses) stay whole."""
+    leaves = {}
+
+    def walk(name, obj):
+        if torch.is_tensor(obj):
+            leaves[name] = obj
+        elif isinstance(obj, dict):
+            for k, v in obj.items():
+                walk(f"{name}.{k}", v)
+        elif isinstance(obj, (list, tuple)):
+            for i, v in enumerate(obj):
+                walk(f"{name}.{i}", v)
+
+    for name, obj in zip(("preds", "loss", "loss_by_type"), out):
+        walk(name, obj)
+    arrays = {k: v.detach().to("cpu", torch.float64 if v.dtype == torch.float64 else torch.float32).numpy()
+              for k, v in leaves.items()}
+    if sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES:
+        rng = np.random.default_rng(20211119)
+        left = DUMP_LIMIT_BYTES
+        order = sorted(arrays, key=lambda k: (arrays[k].nbytes, k))
+        for i, k in enumerate(order):
+            a = arrays[k]
+            cap = left // (len(order) - i)
+            if a.nbytes > cap:
+                keep = max(1, cap // a.itemsize)
+                a = arrays[k] = a.reshape(-1)[np.sort(rng.choice(a.size, keep, replace=False))]
+            left -= a.nbytes
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k.replace(os.sep, "_") + ".npy"), a)
+
+
 def main():
     args = parse()
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
@@ -351,14 +399,19 @@ def run(args):
         first_loss = loss
     if not (loss == loss and abs(loss) < 1e30):
         raise SystemExit(f"bench.py: the training loss is not finite ({loss}): the timed steps did not train")
-    # "did it train": the loss of ONE step is noisy under augmentation (a colour-jittered or cropped batch costs 0.85 where
-    # its neighbours cost 0.2, in eager execution as in the captured step: tools/determinism_train.py ... aug), so the check
-    # compares the first step with the MEDIAN of the last timed step and four more steps run after the timed region
-    tail = [loss]
-    for i in range(4):
-        tail.append(float(trainer.run_a_batch(batches[(args.steps + i) % len(batches)])[1]))
-    torch.cuda.synchronize()
-    settled = sorted(tail)[len(tail) // 2]
+    if args.dump_outputs and rank == 0:
+        # before any later step: a captured step returns its graph's static outputs, which the next replay overwrites
+        dump_outputs(out, args.dump_outputs)
+    settled = None
+    if args.full:
+        # "did it train": the loss of ONE step is noisy under augmentation (a colour-jittered or cropped batch costs 0.85
+        # where its neighbours cost 0.2, in eager execution as in the captured step: tools/determinism_train.py ... aug), so
+        # the check compares the first step with the MEDIAN of the last timed step and four more steps after the timed region
+        tail = [loss]
+        for i in range(4):
+            tail.append(float(trainer.run_a_batch(batches[(args.steps + i) % len(batches)])[1]))
+        torch.cuda.synchronize()
+        settled = sorted(tail)[len(tail) // 2]
     per_step = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
     pick = lambda q: per_step[min(len(per_step) - 1, int(q * len(per_step)))]          # noqa: E731
     step_ms = {"median": round(pick(0.5), 4), "p10": round(pick(0.1), 4), "p90": round(pick(0.9), 4),
@@ -400,14 +453,16 @@ def run(args):
                        "global_batch": global_batch, "per_gpu_batch": args.batch, "mode": mode,
                        "parallelism": f"dp{world}", "ranks": (dist.get_world_size() if world > 1 else 1),
                        "graph_nodes": getattr(step_graph, "census", None),
-                       "first_loss": round(first_loss, 6), "final_loss": round(loss, 6),
-                       "settled_loss": round(settled, 6), "loss_decreased": bool(settled < first_loss)},
+                       "first_loss": round(first_loss, 6), "final_loss": round(loss, 6)},
             "step_ms": step_ms,
             "host_enqueue_ms_per_step": round(1000.0 * host_elapsed / args.steps, 4),
         }
-        if args.nets == "rigid" and not (settled < first_loss) and args.warmup + args.steps >= 10:
-            raise SystemExit(f"bench.py: the loss did not decrease over {args.warmup + args.steps} steps on the same "
-                             f"batches ({first_loss} -> median of the last five steps {settled}): the timed steps did not train")
+        if settled is not None:
+            result["config"].update(settled_loss=round(settled, 6), loss_decreased=bool(settled < first_loss))
+            if args.nets == "rigid" and not (settled < first_loss) and args.warmup + args.steps >= 10:
+                raise SystemExit(f"bench.py: the loss did not decrease over {args.warmup + args.steps} steps on the same "
+                                 f"batches ({first_loss} -> median of the last five steps {settled}): the timed steps did "
+                                 "not train")
         early = getattr(trainer, "_early_start", None)
         if world > 1:
             result["config"]["rank_ms_per_step"] = rank_ms
@@ -424,9 +479,10 @@ def run(args):
                 "overlapped_bytes": (int(flat.numel) - int(early)) * 4 if early is not None else 0,
                 "how": "two-graph step, backward cut between decoder and encoder" if early is not None else "after the step",
                 "collectives_issued": bool(world > 1 or os.environ.get("XPT_DP_FORCE_COLLECTIVES") == "1")}
-        if dist.is_available() and dist.is_initialized() and rank == 0 and "grad_exchange" in (result or {}).get("config", {}):
+        if (args.full and dist.is_available() and dist.is_initialized() and rank == 0
+                and "grad_exchange" in (result or {}).get("config", {})):
             result["config"]["grad_exchange"]["measure_all_reduce"] = True
-    if dist.is_available() and dist.is_initialized():
+    if args.full and dist.is_available() and dist.is_initialized():
         # the all-reduce of the two buckets by itself (every rank takes part): HIP events around 10 back-to-back collectives
         flat = trainer.optimizer.flat
         early = getattr(trainer, "_early_start", None)
@@ -455,6 +511,8 @@ def run(args):
                 "how": "10 back-to-back dist.all_reduce(SUM) of the bucket's fp32 range on this process group, HIP events "
                        "(one rank: RCCL's identity collective -- its launch and copy cost, no link traffic)"}
     note(f"timed region done: {elapsed:.3f} s")
+    if not args.full:
+        return (result if rank == 0 else None), world
     if args.sustained_seconds > 0 and world == 1 and args.config != "c5":
         # a longer stretch of the same steps (outside `value`): long enough for an outside observer's GPU-busy sampling
         torch.cuda.synchronize()
