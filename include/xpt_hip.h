@@ -222,6 +222,35 @@ int xpt_adam_step(float* param, float* grad, float* m, float* v, long long n, co
 int xpt_sgd_step(float* param, float* grad, long long n, float lr, float grad_scale, int zero_grad, void* shadow_bf16,
                  void* stream);
 
+/* ------------------------------------------------------------------ a14b: dynamic loss scaling (half-precision build)
+ * replaces the dynamic loss scale of tf.keras.mixed_precision LossScaleOptimizer (TF 2.4: its DynamicLossScale state --
+ * initial scale, growth_steps, multiplier 2 -- and apply_gradients' "do not apply" branch), entirely on the device: the
+ * backward pass is seeded with `scale`, every step checks the final flat gradient, the optimizer skips the update when it
+ * holds an inf / NaN, and the state is updated behind it without a host round trip.  One 32-byte, 16-byte aligned block: */
+typedef struct xpt_loss_scale_state {
+  float scale;       /* S: the seed of the backward pass (a power of two, >= 1)                          */
+  float inv_scale;   /* 1 / S (exact): the optimizer's unscale factor                                    */
+  int found_inf;     /* != 0: the gradient of this step holds an inf / NaN (raised by xpt_grad_nonfinite) */
+  int good_steps;    /* finite steps since the last change of S                                          */
+  int skipped;       /* steps skipped since the state was created                                        */
+  int reserved[3];
+} xpt_loss_scale_state;
+/* found_inf |= any(g[i] is +-inf or NaN, i < n): exponent-bit test (not folded by fast-math), one device-scope atomic per
+ * workgroup that saw one; g 16-byte aligned. */
+int xpt_grad_nonfinite(const float* g, long long n, void* state, void* stream);
+/* found_inf set:   S = max(S / 2, 1), good_steps = 0, skipped += 1;
+ * found_inf clear: good_steps += 1; at growth_steps: S = 2 S (if finite), good_steps = 0;
+ * then found_inf = 0.  One workgroup; launched after the optimizer has read the state. */
+int xpt_loss_scale_update(void* state, int growth_steps, void* stream);
+/* xpt_adam_step / xpt_sgd_step that read the state: found_inf set -> param, m, v and shadow are left unchanged (grad is
+ * still zeroed when zero_grad != 0; the Adam step count is the caller's and keeps counting, as LossScaleOptimizer's
+ * do-not-apply branch bumps `iterations`); clear -> exactly the static step with grad_scale * inv_scale. */
+int xpt_adam_step_dyn(float* param, float* grad, float* m, float* v, long long n, const float* step, float lr,
+                      float beta1, float beta2, float eps, float grad_scale, int zero_grad, void* shadow_bf16,
+                      const void* state, void* stream);
+int xpt_sgd_step_dyn(float* param, float* grad, long long n, float lr, float grad_scale, int zero_grad, void* shadow_bf16,
+                     const void* state, void* stream);
+
 /* ------------------------------------------------------------------ a2: depthwise convolution (NASNet separable convs)
  * replaces the depthwise half of every keras SeparableConv2D(use_bias=False) inside
  * tf.keras.applications.NASNetMobile (reference call site model/build_model/pretrained_nets.py:36-44), with the

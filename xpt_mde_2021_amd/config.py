@@ -175,6 +175,11 @@ class VodeOptions(LossOptions):
     # is LOSS_SCALE_FP16 instead of 1 (per-pixel gradients of a mean over 4e5 pixels are ~1e-7, below half's 6e-8 .. 6e-5
     # subnormal range), taken out again by the optimizer's grad_scale (a power of two: exact)
     LOSS_SCALE_FP16 = float(__import__("os").environ.get("XPT_LOSS_SCALE_FP16", "32768"))
+    # dynamic loss scaling (fp16 only; model/model_util/loss_scale.py, tf.keras.mixed_precision LossScaleOptimizer's rule):
+    # LOSS_SCALE_FP16 is then the initial scale (a power of two); a step whose gradient holds an inf / NaN is skipped on the
+    # device and halves the scale, LOSS_SCALE_GROWTH_STEPS finite steps in a row double it.  Off: the static scale above
+    LOSS_SCALE_FP16_DYNAMIC = __import__("os").environ.get("XPT_LOSS_SCALE_DYNAMIC", "0") == "1"
+    LOSS_SCALE_GROWTH_STEPS = int(__import__("os").environ.get("XPT_LOSS_SCALE_GROWTH_STEPS", "2000"))
     CHANNELS_LAST = True                      # NHWC activations for MIOpen
     FUSED_LOSS = True                         # fused warp+L1+SSIM march kernels when the loss set allows it
     GRAD_BUCKETS = 1                          # flat gradient buckets per all-reduce (RCCL over xGMI)

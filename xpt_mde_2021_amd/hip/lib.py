@@ -86,6 +86,10 @@ SIGNATURES = {
     "xpt_smooth_ms_bwd": (_i, [_i, _p, _p, _p, _p, _i, _p, _p, _f, _i, _p]),
     "xpt_adam_step": (_i, [_p, _p, _p, _p, ctypes.c_longlong, _p, _f, _f, _f, _f, _f, _i, _p, _p]),
     "xpt_sgd_step": (_i, [_p, _p, ctypes.c_longlong, _f, _f, _i, _p, _p]),
+    "xpt_grad_nonfinite": (_i, [_p, ctypes.c_longlong, _p, _p]),
+    "xpt_loss_scale_update": (_i, [_p, _i, _p]),
+    "xpt_adam_step_dyn": (_i, [_p, _p, _p, _p, ctypes.c_longlong, _p, _f, _f, _f, _f, _f, _i, _p, _p, _p]),
+    "xpt_sgd_step_dyn": (_i, [_p, _p, ctypes.c_longlong, _f, _f, _i, _p, _p, _p]),
     "xpt_dwconv_fwd": (_i, [_p, _p, _p] + [_i] * 12 + [_p]),
     "xpt_dwconv_bwd_data": (_i, [_p, _p, _p, _p] + [_i] * 12 + [_p]),
     "xpt_dwconv_tune": (_i, [_i]),

@@ -282,16 +282,18 @@ def _constant_rows(values, batch, device):
 class _PhotoFusedMS(torch.autograd.Function):
     """photo_fused for every scale of the pyramid in ONE march launch (+ one finishing launch) forward and backward;
     the pose gradient comes back already summed over the scales.
-    args = (T, K, scales, grad_hint, src_0.., depth_0.., target_0..).
+    args = (T, K, scales, grad_hint, hint_scale, src_0.., depth_0.., target_0..).
 
     grad_hint (2 n floats or None): the gradients the caller's loss will send back for (l1 of every scale, ssim of every
     scale) -- they are loss weights over the batch size (TotalLoss.__call__, losses.py:44-55), known before the forward
     runs.  With a hint the forward IS the backward: xpt_photo_march_ms_fwdbwd leaves losses, d_depth and dT in one pass
     (csrc/xpt_march.hip) and backward() hands the stored gradients out after checking the hint against what actually
-    arrived (outside graph capture; a mismatch recomputes with the real gradients)."""
+    arrived (outside graph capture; a mismatch recomputes with the real gradients).
+    hint_scale ([1] device tensor or None): the announced gradients are grad_hint x hint_scale -- the live loss scale of
+    dynamic loss scaling (model_util/loss_scale.py), a power of two, so the product is exact and the check still holds."""
 
     @staticmethod
-    def forward(ctx, T, K, scales, grad_hint, *tensors):
+    def forward(ctx, T, K, scales, grad_hint, hint_scale, *tensors):
         import ctypes
         lib = _lib.load()
         n = len(scales)
@@ -315,11 +317,13 @@ class _PhotoFusedMS(torch.autograd.Function):
         ptrs = lambda ts: P(*[t.data_ptr() for t in ts])       # noqa: E731
         ci, cf = (ctypes.c_int * n)(*hs), (ctypes.c_float * n)(*[float(s) for s in scales])
         cw = (ctypes.c_int * n)(*ws_)
-        needs_grad = any(ctx.needs_input_grad[i] for i in (0,) + tuple(range(4 + n, 4 + 2 * n)))
+        needs_grad = any(ctx.needs_input_grad[i] for i in (0,) + tuple(range(5 + n, 5 + 2 * n)))
         one_pass = (grad_hint is not None and needs_grad and _ONE_PASS and not _MARCH_V1 and len(grad_hint) == 2 * n)
         ctx.stash = None
         if one_pass:
             hint = _constant_rows(grad_hint, B, T.device)
+            if hint_scale is not None:
+                hint = hint * hint_scale            # one element-wise launch inside the step: S x coefficients
             ddepths = [torch.empty_like(d) for d in depths]
             dT = torch.empty_like(T)
             _lib.check(lib.xpt_photo_march_ms_fwdbwd(n, ptrs(srcs), ptrs(depths), _ptr(T), _ptr(K), ptrs(targets),
@@ -357,7 +361,7 @@ class _PhotoFusedMS(torch.autograd.Function):
                     not torch.cuda.is_current_stream_capturing()) and all(
                     (g is None and not bool(hint[i].any())) or (g is not None and torch.equal(g.reshape(-1), hint[i]))
                     for i, g in enumerate(grads)):
-                return (dT, None, None, None, *([None] * n), *ddepths, *([None] * n))
+                return (dT, None, None, None, None, *([None] * n), *ddepths, *([None] * n))
             if not torch.cuda.is_current_stream_capturing():
                 PHOTO_HINT_MISSES.append(tuple(None if g is None else float(g.reshape(-1)[0]) for g in grads))
         zero = None
@@ -377,7 +381,7 @@ class _PhotoFusedMS(torch.autograd.Function):
         _lib.check(bwd(n, ptrs(srcs), ptrs(depths), _ptr(T), _ptr(K), ptrs(targets), ptrs(gs[:n]), ptrs(gs[n:]),
                        ptrs(ddepths), _ptr(dT), _ptr(ws), nws, B, N, (ctypes.c_int * n)(*hs), (ctypes.c_int * n)(*ws_),
                        (ctypes.c_float * n)(*scales), _stream()), "xpt_photo_march_ms_bwd")
-        return (dT, None, None, None, *([None] * n), *ddepths, *([None] * n))
+        return (dT, None, None, None, None, *([None] * n), *ddepths, *([None] * n))
 
 
 PHOTO_HINT_CHECK = True       # False: trust the announced gradients (no device fetch in eager steps)
@@ -387,12 +391,14 @@ PHOTO_HINT_MISSES = []        # announced-vs-actual mismatches seen by backward(
 def photo_fused_multi_scale(srcs, depths, T, K, targets, scales, grad_hint=None):
     """[(l1 [B], ssim [B]) per scale] of photo_fused, all scales in one launch (N must be 4 or 1, at most 4 scales).
     grad_hint: ([d total / d l1_s] per scale, [d total / d ssim_s] per scale) as floats when the caller knows them (loss
-    weights over the batch size): forward and backward then run as ONE pass (see _PhotoFusedMS)."""
+    weights over the batch size): forward and backward then run as ONE pass (see _PhotoFusedMS).  A third entry of
+    grad_hint, a [1] device tensor, multiplies the announced gradients inside the step (dynamic loss scaling)."""
     n = len(scales)
-    hint = None
+    hint, hint_scale = None, None
     if grad_hint is not None:
         hint = tuple(float(v) for v in grad_hint[0]) + tuple(float(v) for v in grad_hint[1])
-    out = _PhotoFusedMS.apply(T, K, tuple(scales), hint, *srcs, *depths, *targets)
+        hint_scale = grad_hint[2] if len(grad_hint) > 2 else None
+    out = _PhotoFusedMS.apply(T, K, tuple(scales), hint, hint_scale, *srcs, *depths, *targets)
     return [(out[i], out[n + i]) for i in range(n)]
 
 

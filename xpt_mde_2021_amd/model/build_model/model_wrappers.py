@@ -58,8 +58,8 @@ def load_logical_state_dict(model, state):
 class ModelWrapper:
     def __init__(self, models):
         self.models = models                      # {"depthnet": nn.Module, "posenet": nn.Module}
-        # (BASELINE configs[4] names fp16 convolutions: this build computes them in bf16 -- same matrix-core rate on gfx950,
-        #  fp32 accumulation, no loss scaling; DESIGN.md section 7 -- so "fp16" is not an accepted value)
+        # (bf16, the default, needs no loss scaling; "fp16" -- BASELINE configs[4], fp16 convolutions -- loads the IEEE-half build
+        #  of the library and trains with a static or dynamic loss scale, config.LOSS_SCALE_FP16 / LOSS_SCALE_FP16_DYNAMIC)
         if opts.CONV_DTYPE in ("bf16", "fp16"):
             # the 16-bit format is a property of the loaded library (hip/lib.py): one per process
             from ...hip import lib as _lib

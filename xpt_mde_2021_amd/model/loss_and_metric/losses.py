@@ -27,6 +27,7 @@ class TotalLoss:
                            so that data-parallel gradients are SUMMED across replicas)
         """
         self.loss_objects = loss_objects
+        self.hint_scale = None         # dynamic loss scaling: the live device scale of the trainer (see _photo_grad_hint)
         self.loss_weights = loss_weights
         self.stereo = stereo
         self.batch_size = batch_size
@@ -46,8 +47,11 @@ class TotalLoss:
         with this key suffix reads: weight of the loss type x scale weight / global batch (the coefficients __call__
         applies below), or None when they cannot be told in advance."""
         out = {"L1": [0.0] * nscales, "SSIM": [0.0] * nscales}
-        # (the fp16 configuration seeds the backward pass with its static loss scale, train_val.ModelTrainer.loss_seed)
-        seed = float(opts.LOSS_SCALE_FP16) if opts.CONV_DTYPE == "fp16" else 1.0
+        # (the fp16 configuration seeds the backward pass with its static loss scale, train_val.ModelTrainer.loss_seed;
+        # with dynamic loss scaling the trainer sets hint_scale, the live device scale: the coefficients are announced at
+        # seed 1 and multiplied by it inside the step)
+        hint_scale = getattr(self, "hint_scale", None)
+        seed = 1.0 if hint_scale is not None else float(opts.LOSS_SCALE_FP16) if opts.CONV_DTYPE == "fp16" else 1.0
         try:
             for name, obj in (self.loss_objects or {}).items():
                 if type(obj) is not cls or getattr(obj, "key_suffix", "") != suffix or obj.method not in out:
@@ -59,6 +63,8 @@ class TotalLoss:
                     out[obj.method][i] += seed * float(self.loss_weights[name]) * weights[i] / self.batch_size
         except (KeyError, TypeError, ValueError):
             return None
+        if hint_scale is not None:
+            return out["L1"], out["SSIM"], hint_scale
         return out["L1"], out["SSIM"]
 
     def __call__(self, predictions, features):

@@ -161,37 +161,61 @@ class KerasAdam:
             raise WrongInputException("apply_gradients: an L2 term needs the whole buffer in one piece")
         return lo, hi
 
-    def apply_gradients(self, grad_scale=1.0, zero_grad=True, lo=0, hi=None, bump=True):
-        """optimizer.apply_gradients (train_val.py:86) on the flat buffers; hipGraph-capturable.  [lo, hi): a piece of the
-        buffers (element-wise update: pieces are independent; the trainer that applies a step in pieces counts the step once,
-        begin_step(), and passes bump=False)."""
+    def _begin_update(self, grad_scale, lo, hi, bump, scaler):
+        """Shared head of apply_gradients: the piece, the step count, the L2 terms and -- dynamic loss scaling -- the check
+        of the now final gradient."""
         f = self.flat
         lo, hi = self._piece(lo, hi)
+        if scaler is not None and (lo, hi) != (0, f.numel):
+            raise WrongInputException("apply_gradients: dynamic loss scaling skips or applies the whole buffer in one piece")
         if bump:
             self.step_count += 1
         for a, b, coef in self._ranges():
-            f.grad[a:b].add_(f.data[a:b], alpha=coef / float(grad_scale))
+            if scaler is None:
+                f.grad[a:b].add_(f.data[a:b], alpha=coef / float(grad_scale))
+            else:       # the gradient is scaled by the DEVICE scale S: coefficient * S * w (one capturable launch)
+                f.grad[a:b].addcmul_(f.data[a:b], scaler.scale_tensor, value=coef / float(grad_scale))
+        if scaler is not None:
+            scaler.check(f.grad)
+        return lo, hi
+
+    def apply_gradients(self, grad_scale=1.0, zero_grad=True, lo=0, hi=None, bump=True, scaler=None):
+        """optimizer.apply_gradients (train_val.py:86) on the flat buffers; hipGraph-capturable.  [lo, hi): a piece of the
+        buffers (element-wise update: pieces are independent; the trainer that applies a step in pieces counts the step once,
+        begin_step(), and passes bump=False).  scaler (loss_scale.DynamicLossScale): the gradient is scaled by the scaler's
+        device scale S; the update is skipped when it holds an inf / NaN and otherwise unscaled by grad_scale / S."""
+        f = self.flat
+        lo, hi = self._begin_update(grad_scale, lo, hi, bump, scaler)
         if f.data.is_cuda:
             lib = _lib.load()
-            _lib.check(lib.xpt_adam_step(f.data.data_ptr() + 4 * lo, f.grad.data_ptr() + 4 * lo, self.m.data_ptr() + 4 * lo,
-                                         self.v.data_ptr() + 4 * lo, hi - lo, self.step_count.data_ptr(), self.lr, self.b1,
-                                         self.b2, self.eps, float(grad_scale), int(zero_grad),
-                                         None if f.shadow is None else f.shadow.data_ptr() + f.shadow.element_size() * lo,
-                                         torch.cuda.current_stream().cuda_stream),
-                       "xpt_adam_step")
+            args = (f.data.data_ptr() + 4 * lo, f.grad.data_ptr() + 4 * lo, self.m.data_ptr() + 4 * lo,
+                    self.v.data_ptr() + 4 * lo, hi - lo, self.step_count.data_ptr(), self.lr, self.b1, self.b2, self.eps,
+                    float(grad_scale), int(zero_grad),
+                    None if f.shadow is None else f.shadow.data_ptr() + f.shadow.element_size() * lo)
+            stream = torch.cuda.current_stream().cuda_stream
+            if scaler is None:
+                _lib.check(lib.xpt_adam_step(*args, stream), "xpt_adam_step")
+            else:
+                _lib.check(lib.xpt_adam_step_dyn(*args, scaler.state.data_ptr(), stream), "xpt_adam_step_dyn")
+                scaler.update()
             return
         if (lo, hi) != (0, f.numel):
             raise WrongInputException("apply_gradients: pieces are a device feature")
         # host tensors (CPU-only unit tests of the data-parallel host logic): same arithmetic with tensor ops
         with torch.no_grad():
-            t = self.step_count
-            lr_t = self.lr * torch.sqrt(1 - self.b2 ** t) / (1 - self.b1 ** t)
-            g = f.grad * grad_scale
-            self.m.mul_(self.b1).add_(g, alpha=1 - self.b1)
-            self.v.mul_(self.b2).addcmul_(g, g, value=1 - self.b2)
-            f.data.sub_(lr_t * self.m / (torch.sqrt(self.v) + self.eps))
+            if scaler is None or not scaler.skipped_step():
+                if scaler is not None:
+                    grad_scale = float(torch.tensor(grad_scale, dtype=torch.float32) * scaler.inv_scale())
+                t = self.step_count
+                lr_t = self.lr * torch.sqrt(1 - self.b2 ** t) / (1 - self.b1 ** t)
+                g = f.grad * grad_scale
+                self.m.mul_(self.b1).add_(g, alpha=1 - self.b1)
+                self.v.mul_(self.b2).addcmul_(g, g, value=1 - self.b2)
+                f.data.sub_(lr_t * self.m / (torch.sqrt(self.v) + self.eps))
             if zero_grad:
                 f.grad.zero_()
+            if scaler is not None:
+                scaler.update()
 
 
 class KerasSGD(KerasAdam):
@@ -208,26 +232,31 @@ class KerasSGD(KerasAdam):
         self.step_count = torch.zeros(1, dtype=torch.float32, device=self.flat.data.device)
         return self.flat
 
-    def apply_gradients(self, grad_scale=1.0, zero_grad=True, lo=0, hi=None, bump=True):
+    def apply_gradients(self, grad_scale=1.0, zero_grad=True, lo=0, hi=None, bump=True, scaler=None):
         f = self.flat
-        lo, hi = self._piece(lo, hi)
-        if bump:
-            self.step_count += 1
-        for a, b, coef in self._ranges():
-            f.grad[a:b].add_(f.data[a:b], alpha=coef / float(grad_scale))
+        lo, hi = self._begin_update(grad_scale, lo, hi, bump, scaler)
         if f.data.is_cuda:
             lib = _lib.load()
-            _lib.check(lib.xpt_sgd_step(f.data.data_ptr() + 4 * lo, f.grad.data_ptr() + 4 * lo, hi - lo, self.lr, float(grad_scale),
-                                        int(zero_grad),
-                                        None if f.shadow is None else f.shadow.data_ptr() + f.shadow.element_size() * lo,
-                                        torch.cuda.current_stream().cuda_stream), "xpt_sgd_step")
+            args = (f.data.data_ptr() + 4 * lo, f.grad.data_ptr() + 4 * lo, hi - lo, self.lr, float(grad_scale), int(zero_grad),
+                    None if f.shadow is None else f.shadow.data_ptr() + f.shadow.element_size() * lo)
+            stream = torch.cuda.current_stream().cuda_stream
+            if scaler is None:
+                _lib.check(lib.xpt_sgd_step(*args, stream), "xpt_sgd_step")
+            else:
+                _lib.check(lib.xpt_sgd_step_dyn(*args, scaler.state.data_ptr(), stream), "xpt_sgd_step_dyn")
+                scaler.update()
             return
         if (lo, hi) != (0, f.numel):
             raise WrongInputException("apply_gradients: pieces are a device feature")
         with torch.no_grad():
-            f.data.sub_(f.grad, alpha=self.lr * float(grad_scale))
+            if scaler is None or not scaler.skipped_step():
+                if scaler is not None:
+                    grad_scale = float(torch.tensor(grad_scale, dtype=torch.float32) * scaler.inv_scale())
+                f.data.sub_(f.grad, alpha=self.lr * float(grad_scale))
             if zero_grad:
                 f.grad.zero_()
+            if scaler is not None:
+                scaler.update()
 
 
 def optimizer_factory(opt_name, basic_lr, epoch=0):

@@ -22,6 +22,7 @@ from ..hip import ops as _ops
 from ..utils import util_class as uc
 from ..utils import util_funcs as uf
 from .model_util.distributer import DistributionStrategy
+from .model_util.loss_scale import DynamicLossScale
 from .model_util.optimizers import KerasAdam
 
 
@@ -94,11 +95,16 @@ class TrainValBase:
                 if self.steps_per_epoch and step + 1 >= self.steps_per_epoch:
                     break
         print("")
+        steps = len(results)
         results = pd.DataFrame(fetch_results(results))
         mean_results = results.mean(axis=0).to_dict()
         message = f"[{self.train_val_name} Epoch MEAN], result: " + ", ".join(f"{k}={v:1.4f}" for k, v in mean_results.items())
-        print(message, "\n\n")
+        print(message + self.epoch_note(steps), "\n\n")
         return results, epoch_time.duration / 3600.
+
+    def epoch_note(self, steps):
+        """Extra text for the epoch message (the training loop's dynamic loss scale)."""
+        return ""
 
     def run_a_batch(self, features):
         raise NotImplementedError()
@@ -109,25 +115,39 @@ class TrainValBase:
 
 
 class ModelTrainer(TrainValBase):
+    scaler = None               # loss_scale.DynamicLossScale in the dynamic fp16 mode
+
     def __init__(self, model, loss_object, steps_per_epoch, stereo, augmenter, optimizer):
         super().__init__(model, loss_object, steps_per_epoch, stereo, augmenter, optimizer)
         self.set_name("Train (eager)")
         if isinstance(optimizer, KerasAdam) and optimizer.flat is None:
             groups = model.weight_groups() if hasattr(model, "weight_groups") else None
             optimizer.bind(model.trainable_weights(), groups=groups)
+        # dynamic loss scaling (fp16 only, config.LOSS_SCALE_FP16_DYNAMIC): the scale lives on the device, the loss object's
+        # gradient hint for the one-pass march is built at seed 1 and multiplied by it inside the step
+        self.scaler = None
+        if (opts.CONV_DTYPE == "fp16" and getattr(opts, "LOSS_SCALE_FP16_DYNAMIC", False)
+                and getattr(optimizer, "flat", None) is not None):
+            self.scaler = DynamicLossScale(opts.LOSS_SCALE_FP16, getattr(opts, "LOSS_SCALE_GROWTH_STEPS", 2000),
+                                           device=optimizer.flat.data.device)
+            if hasattr(loss_object, "hint_scale"):          # (TotalLoss)
+                loss_object.hint_scale = self.scaler.scale_tensor
 
     def run_a_batch(self, features):
         return self.train_a_step(features)
 
     def loss_seed(self, total_loss):
         """Seed of the backward pass: None (= 1), or the static loss scale of the fp16 configuration (config.LOSS_SCALE_FP16;
-        a persistent tensor: no launch inside the captured step).  grad_unscale() takes it out again in the optimizer."""
+        a persistent tensor: no launch inside the captured step).  grad_unscale() takes it out again in the optimizer.
+        Dynamic loss scaling: the scaler's live device scale (the optimizer's _dyn kernels take it out)."""
         forced = os.environ.get("XPT_TEST_FORCE_SEED")      # tests: a seed the loss object's gradient hint does not know about
         if forced and total_loss.is_cuda:
             seed = getattr(self, "_loss_seed", None)
             if seed is None:
                 seed = self._loss_seed = torch.full_like(total_loss, float(forced))
             return seed
+        if self.scaler is not None:
+            return self.scaler.seed_like(total_loss)
         if opts.CONV_DTYPE != "fp16" or not total_loss.is_cuda:
             return None
         seed = getattr(self, "_loss_seed", None)
@@ -135,12 +155,28 @@ class ModelTrainer(TrainValBase):
             seed = self._loss_seed = torch.full_like(total_loss, float(opts.LOSS_SCALE_FP16))
         return seed
 
-    @staticmethod
-    def grad_unscale():
+    def grad_unscale(self):
         forced = os.environ.get("XPT_TEST_FORCE_SEED")
         if forced:
             return 1.0 / float(forced)
+        if self.scaler is not None:
+            return 1.0                  # the _dyn optimizer kernels apply 1 / S from the device
         return 1.0 / float(opts.LOSS_SCALE_FP16) if opts.CONV_DTYPE == "fp16" else 1.0
+
+    def loss_scale_state(self):
+        """Dynamic loss scaling: {scale, inv_scale, found_inf, good_steps, skipped} (one device fetch); None otherwise."""
+        return None if self.scaler is None else self.scaler.read()
+
+    def epoch_note(self, steps):
+        if self.scaler is None:
+            return ""
+        scale, skipped, all_skipped = self.scaler.epoch_report(steps)
+        if all_skipped:
+            import sys
+            print(f"[{self.train_val_name}] WARNING: dynamic loss scaling skipped EVERY one of the {steps} steps of this epoch "
+                  f"(the gradient held inf / NaN each time; loss scale now {scale:g}): the weights did not change",
+                  file=sys.stderr, flush=True)
+        return f", loss_scale={scale:g}, skipped_steps={skipped}"
 
     def forward_backward(self, features):
         if self.augmenter is not None:
@@ -254,13 +290,15 @@ class ModelTrainer(TrainValBase):
         state = [opt.flat.data, opt.flat.grad, opt.m, opt.v, opt.step_count]
         if getattr(opt.flat, "shadow", None) is not None:
             state.append(opt.flat.shadow)
+        if self.scaler is not None:
+            state.append(self.scaler.state)       # int32: outside the replay check's finiteness / magnitude bound
         return state
 
     def train_a_step(self, features):
         """train_val.py:78-92: augment -> model -> loss -> gradients -> optimizer.apply_gradients."""
         out = self.forward_backward(features)
         self.reduce_gradients()
-        self.optimizer.apply_gradients(grad_scale=self.grad_unscale())
+        self.optimizer.apply_gradients(grad_scale=self.grad_unscale(), scaler=self.scaler)
         return out
 
 
@@ -632,8 +670,10 @@ class ModelTrainerGraph(ModelTrainer):
         # update of those parameters run on the side stream while the encoder's backward occupies the main one -- 0.1 ms of
         # memory streaming off the critical chain of the captured step.  Element-wise update, disjoint buffer pieces, the
         # same partial sums in the same order: bit-identical to the one-piece step (tests/test_graph_replay.py).
+        # (dynamic loss scaling skips or applies the WHOLE buffer once the whole gradient is known: the one-piece step)
         self._early_start = None
         if (getattr(opts, "EARLY_UPDATE", False) and not self.trains_flow_net and getattr(optimizer, "flat", None) is not None
+                and self.scaler is None
                 and optimizer.flat.data.is_cuda and not getattr(optimizer, "l2_terms", None) and type(model).__name__ == "ModelWrapper"):
             self._early_start = self._find_early_bucket()
             if self._early_start is not None and self._early_start % 4:
@@ -670,7 +710,7 @@ class ModelTrainerGraph(ModelTrainer):
     def _plain_step_with_cut(self, features):
         carry, out = self.backward_first(features)
         self.backward_second(carry)
-        self.optimizer.apply_gradients(grad_scale=self.grad_unscale())
+        self.optimizer.apply_gradients(grad_scale=self.grad_unscale(), scaler=self.scaler)
         return out
 
     def run_a_batch(self, features):
@@ -756,7 +796,7 @@ class ModelTrainerDistrib(ModelTrainer):
         else:
             out = self.forward_backward(features)
         self.reduce_gradients()
-        self.optimizer.apply_gradients(grad_scale=self.grad_unscale())
+        self.optimizer.apply_gradients(grad_scale=self.grad_unscale(), scaler=self.scaler)
         return out
 
 
