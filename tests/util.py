@@ -65,3 +65,56 @@ def flip_safe_depth(depth, T, K, scale, eps=1e-3, nudge=False):
     # what is left does not move with its depth (no parallax along that axis): its d_depth term is as insensitive as its
     # projection, and it is one pixel in a sum for the pose gradient
     return out, share
+
+
+# ------------------------------------------------------------------------------------------------ parameter gradients
+def grad_table(got, ref):
+    """Per-tensor errors of the gradients `got` against `ref` (both {name: tensor}), worst first:
+    [(name, shape, rel-L2 = |g - g_ref| / |g_ref|, cosine, |g_ref|)].  Both must name exactly the same parameters (none
+    skipped, none extra), with equal shapes and finite values."""
+    missing, extra = sorted(set(ref) - set(got)), sorted(set(got) - set(ref))
+    assert not missing and not extra, (f"gradients missing for {len(missing)} parameters {missing[:6]}, "
+                                       f"extra ones for {len(extra)} {extra[:6]}")
+    rows = []
+    for name, r in ref.items():
+        g, r = got[name].detach().double().cpu(), r.detach().double().cpu()
+        assert g.shape == r.shape, f"{name}: shape {tuple(g.shape)}, reference {tuple(r.shape)}"
+        assert bool(torch.isfinite(g).all()), f"{name}: non-finite gradient"
+        assert bool(torch.isfinite(r).all()), f"{name}: non-finite reference gradient"
+        shape = tuple(g.shape)
+        g, r = g.reshape(-1), r.reshape(-1)
+        nr, ng, nd = float(r.norm()), float(g.norm()), float((g - r).norm())
+        rel = nd / nr if nr > 0 else (0.0 if nd == 0 else float("inf"))
+        cos = float(g @ r) / (ng * nr) if ng > 0 and nr > 0 else float(ng == nr)
+        rows.append((name, shape, rel, cos, nr))
+    rows.sort(key=lambda row: -row[2])
+    return rows
+
+
+def median_rel(rows):
+    rel = sorted(row[2] for row in rows)
+    return rel[len(rel) // 2]
+
+
+def flagged(rows, bar):
+    """Names of the parameters whose rel-L2 exceeds `bar`."""
+    return {row[0] for row in rows if row[2] > bar}
+
+
+def print_grad_table(rows, what, top=20):
+    rel = sorted(row[2] for row in rows)
+    print(f"\n[{what}] {len(rows)} parameter gradients, rel-L2 median {median_rel(rows):.2e}, "
+          f"90 % {rel[len(rel) * 9 // 10]:.2e}, max {rel[-1]:.2e}")
+    print(f"  {'parameter':<60} {'shape':<20} {'rel-L2':>9} {'cosine':>10} {'|g_ref|':>9}")
+    for name, shape, r, c, n in rows[:top]:
+        print(f"  {name:<60} {str(shape):<20} {r:9.2e} {c:10.6f} {n:9.2e}")
+
+
+def assert_grads_close(got, ref, per_tensor, median, what):
+    """grad_table + print_grad_table, then every tensor within rel-L2 `per_tensor` and the median within `median`."""
+    rows = grad_table(got, ref)
+    print_grad_table(rows, what)
+    bad = [(n, r) for n, _, r, _, _ in rows if r > per_tensor]
+    assert not bad, f"{what}: {len(bad)} gradients above rel-L2 {per_tensor:g}: " + ", ".join(f"{n} {r:.2e}" for n, r in bad[:10])
+    assert median_rel(rows) <= median, f"{what}: median rel-L2 {median_rel(rows):.2e} > {median:g}"
+    return rows

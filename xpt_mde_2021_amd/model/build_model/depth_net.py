@@ -96,8 +96,10 @@ class ScaledDepthHead(nn.Module):
                     conv, src_alias = _conv.head_conv_split(src, self.conv.conv.weight, self.conv.conv.bias)
                 else:
                     conv = _conv.head_conv(src, self.conv.conv.weight, self.conv.conv.bias)     # bf16 features in, fp32 prediction out
-            else:
+            elif src.is_cuda:
                 conv = self.conv(src.float())
+            else:                       # (CPU: the layer's own dtype -- fp64 for the reference step of oracle/ref_step.py)
+                conv = self.conv(src.to(self.conv.conv.weight.dtype))
             if not activate:
                 depth, self.last_disp = None, None
             elif hasattr(self.predict_depth, "with_disparity"):

@@ -45,8 +45,10 @@ class PoseNetBasic(nn.Module):
         if x.is_cuda and x.dtype in (torch.float32, _half()):
             from ...hip import ops as _ops
             poses = _ops.global_avg_pool(x)                    # GlobalAveragePooling2D (cast included), one launch
-        else:
+        elif x.is_cuda:
             poses = x.float().mean(dim=(2, 3))                 # GlobalAveragePooling2D
+        else:                                                  # (CPU: the head's own dtype, fp64 in oracle/ref_step.py)
+            poses = x.to(self.head.conv.weight.dtype).mean(dim=(2, 3))
         return {"pose": poses.reshape(-1, self.numsrc, 6)}
 
 
