@@ -744,6 +744,38 @@ int xpt_sepconv_bn_multi_fwd(int n, const void* const* x, const float* const* wd
                              void* const* yb, const void* const* residual, void* const* y, float eps, int B, int H, int W,
                              int C, int cout, void* stream);
 
+/* ------------------------------------------------------------------ MobileNetV2 depthwise stage (csrc/xpt_mbconv.hip)
+ * DepthwiseConv2D 3x3 -> BatchNormalization (moving statistics) -> ReLU6: the middle of _inverted_res_block of
+ * tf.keras.applications.MobileNetV2(include_top=False), one of the backbones model/build_model/pretrained_nets.py:31-34
+ * instantiates.  x [B,H,W,C], y [B,OH,OW,C] NHWC in the 16-bit format of the build, w [C][3][3], gamma / beta / mean / var [C]
+ * fp32, fp32 accumulation.  a(v) = clamp(v, 0, 6) when act_in (the ReLU6 of the PRECEDING BatchNorm, whose output is stored
+ * pre-activation), else v:
+ *   u = sum_{ky,kx<3} w[c,ky,kx] a(x[b, oy stride + ky - pad_t, ox stride + kx - pad_l, c])   (zero outside the input)
+ *   y = clamp(s[c] u + t[c], 0, 6),  s = gamma rsqrt(var + eps),  t = beta - mean s
+ * stride in {1, 2}, pad_t / pad_l in {0, 1}, the centre of every window inside the input (SAME padding), C % 8 == 0 and
+ * 16-byte aligned pointers (else XPT_ERR_ARG / XPT_ERR_SHAPE before any launch), tensors below 2 GiB. */
+int xpt_dwconv_bn_relu6_fwd(const void* x, const float* w, const float* gamma, const float* beta, const float* mean,
+                            const float* var, float eps, void* y, int B, int H, int W, int C, int stride, int pad_t, int pad_l,
+                            int OH, int OW, int act_in, void* stream);
+/* Launch plan of the forward: a lane computes 1, 2 or 4 neighbouring outputs of a row -- as many as still leave two workgroups
+ * per CU.  xpt_dwconv_bn_relu6_fwd_outputs() answers what a call with these sizes will use; xpt_dwconv_bn_relu6_tune(n) forces
+ * n in {1, 2, 4} process-wide (0: automatic again; anything else XPT_ERR_ARG) -- benchmarking, and tests of every variant on
+ * small maps.  Same results whatever the plan. */
+int xpt_dwconv_bn_relu6_tune(int fwd_outputs);
+int xpt_dwconv_bn_relu6_fwd_outputs(int B, int OH, int OW, int C);
+/* Its whole backward in ONE launch.  gz = dy [0 < y < 6] (mask from the stored y; no gradient at exactly 0 and 6, as
+ * tf.nn.relu6); dx = a'(x) s sum_k w_k gz (a'(x) = [0 < x < 6] when act_in: the gradient w.r.t. the preceding BatchNorm's
+ * output); dx may be NULL.  dy is read with a pixel pitch (elements, % 8 == 0): a channel slice is consumed in place.
+ * partials: chunks = xpt_dwconv_bn_relu6_bwd_chunks() rows of 11 C floats, in parameter units (rows simply add; fixed order,
+ * no atomics): with G[c,k] = sum gz a(x)[tap k] a row is [C][9] s G (dL/dw) | [C] rsqrt(var + eps) (sum_k w_k G_k - mean
+ * sum gz) (dL/dgamma: the derivative of s u + beta - mean s; sum gz u = sum_k w_k G_k) | [C] sum gz (dL/dbeta) -- three
+ * contiguous pieces, each a job of xpt_reduce_partials with stride 11 C. */
+int xpt_dwconv_bn_relu6_bwd_chunks(int B, int OH, int OW, int C);
+int xpt_dwconv_bn_relu6_bwd(const void* x, const void* y, const void* dy, long long dy_pitch, const float* w,
+                            const float* gamma, const float* mean, const float* var, float eps, void* dx, float* partials,
+                            size_t partial_floats, int B, int H, int W, int C, int stride, int pad_t, int pad_l, int OH, int OW,
+                            int act_in, void* stream);
+
 /* ------------------------------------------------------------------ captured-step audit (no reference counterpart)
  * Node census of a captured hipGraph (hipGraph_t as torch.cuda.CUDAGraph(keep_graph=True).raw_cuda_graph() hands it out),
  * child graphs included: counts[6] = kernel, memcpy, memset, host, other nodes, total.  The trainers that replace the

@@ -1,0 +1,264 @@
+"""xpt_dwconv_bn_relu6_fwd / _bwd (csrc/xpt_mbconv.hip) through the C ABI of BOTH libraries (bf16, IEEE half) against fp64:
+depthwise 3x3 -> BatchNorm -> ReLU6 of tf.keras.applications.MobileNetV2's _inverted_res_block (the backbone
+model/build_model/pretrained_nets.py:31-34 instantiates), with the preceding ReLU6 optionally applied on load (act_in).
+
+Bounds.  Forward and dx (16-bit outputs): |err| <= 2^-8 |ref| + 1e-4 max|ref| for bf16, 2^-11 for IEEE half -- the output
+format's rounding plus the project's 1e-4 bar for fp32 arithmetic against fp64.  dw / dgamma / dbeta (fp32, chunk-summed):
+1e-4 max|ref|.  The backward's ReLU6 mask comes from the STORED 16-bit y: where the fp64 s u + t lies within 2^-7 * 6 of 0 or
+of 6 the store may legitimately land on the other side, so dy is set to zero there ON BOTH SIDES (share printed, <= 5 %, asserted
+on the CPU from the fp64 reference); everything else is compared with nothing excluded."""
+import ctypes
+import functools
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+pytestmark = pytest.mark.gpu
+
+EPS = 1e-3
+SHAPES = [(2, 5, 7, 8, 1), (2, 6, 10, 24, 2), (1, 9, 5, 16, 2), (2, 2, 3, 960, 1), (2, 4, 6, 576, 2), (8, 16, 24, 96, 2)]
+FORMATS = {"bf16": (torch.bfloat16, 2.0 ** -8), "fp16": (torch.float16, 2.0 ** -11)}
+
+
+@functools.lru_cache(maxsize=None)
+def library(fmt):
+    from xpt_mde_2021_amd.hip import lib as xl
+    lib = ctypes.CDLL(xl.LIB_PATH_F16 if fmt == "fp16" else xl.LIB_PATH)
+    for name in ("xpt_dwconv_bn_relu6_fwd", "xpt_dwconv_bn_relu6_bwd_chunks", "xpt_dwconv_bn_relu6_bwd", "xpt_half_format"):
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = xl.SIGNATURES[name]
+    assert lib.xpt_half_format() == (1 if fmt == "fp16" else 0)
+    return lib
+
+
+def same_pads(h, w, stride):
+    if stride == 1:
+        return 1, 1, 1, 1, h, w
+    oh, ow = -(-h // 2), -(-w // 2)
+    th, tw = (oh - 1) * 2 + 3 - h, (ow - 1) * 2 + 3 - w
+    return th // 2, th - th // 2, tw // 2, tw - tw // 2, oh, ow
+
+
+@functools.lru_cache(maxsize=None)
+def case(shape, act_in, fmt):
+    """Inputs (rounded to the 16-bit format) and the fp64 reference of one case, computed once on the CPU; never modified."""
+    B, H, W, C, stride = shape
+    dtype, _ = FORMATS[fmt]
+    g = torch.Generator().manual_seed(1000 * C + 10 * H + stride + (7 if act_in else 0))
+    rnd = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)                  # noqa: E731
+    x = (2.5 + 3.0 * rnd(B, C, H, W)).to(dtype).double()                                # both clamps of act_in act
+    w = rnd(C, 1, 3, 3).float().double() / 3.0
+    w = w.float().double()
+    gamma = (0.5 + torch.rand(C, generator=g, dtype=torch.float64)).float().double()
+    var = (0.5 + 1.5 * torch.rand(C, generator=g, dtype=torch.float64)).float().double()
+    pt, pb, pl, pr, OH, OW = same_pads(H, W, stride)
+    a = x.clamp(0, 6) if act_in else x
+    u = F.conv2d(F.pad(a, (pl, pr, pt, pb)), w, None, stride, 0, 1, C)
+    # moving mean at the channel's own mean of u, beta at 3 +- 1: y spreads over [0, 6] and beyond on both sides
+    mean = (u.mean((0, 2, 3)) + 0.5 * rnd(C)).float().double()
+    beta = (3.0 + rnd(C)).float().double()
+    gamma = (gamma * (var + EPS).sqrt() * 3.0 / u.std().clamp_min(0.1)).float().double()   # s u has a spread of about 3
+    xr, wr, gr, br = (t.clone().requires_grad_(True) for t in (x, w, gamma, beta))
+    ar = F.hardtanh(xr, 0.0, 6.0) if act_in else xr
+    ur = F.conv2d(F.pad(ar, (pl, pr, pt, pb)), wr, None, stride, 0, 1, C)
+    s = gr / (var + EPS).sqrt()
+    v = ur * s.view(1, C, 1, 1) + (br - mean * s).view(1, C, 1, 1)
+    y = F.hardtanh(v, 0.0, 6.0)
+    shares = (float((y == 0).double().mean()), float(((y > 0) & (y < 6)).double().mean()), float((y == 6).double().mean()))
+    delta = 6.0 * 2.0 ** -7
+    zone = (v.detach().abs() < delta) | ((v.detach() - 6.0).abs() < delta)
+    dy = rnd(B, C, OH, OW).to(dtype).double()
+    dy[zone] = 0.0
+    (y * dy).sum().backward()
+    ref = dict(y=y.detach(), dx=xr.grad, dw=wr.grad, dgamma=gr.grad, dbeta=br.grad)
+    return dict(x=x, w=w, gamma=gamma, beta=beta, mean=mean, var=var, dy=dy, ref=ref, shares=shares,
+                zeroed=float(zone.double().mean()), geom=(pt, pl, OH, OW))
+
+
+def nhwc(t, dtype, dev):
+    """NCHW fp64 CPU tensor -> dense NHWC 16-bit device tensor."""
+    return t.permute(0, 2, 3, 1).contiguous().to(dtype).to(dev)
+
+
+def ptr(t):
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def run(lib, dev, fmt, shape, act_in, c, dy_dev, dy_pitch, want_dx=True):
+    B, H, W, C, stride = shape
+    dtype, _ = FORMATS[fmt]
+    pt, pl, OH, OW = c["geom"]
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    x = nhwc(c["x"], dtype, dev)
+    w, gamma, beta, mean, var = (c[k].float().contiguous().to(dev) for k in ("w", "gamma", "beta", "mean", "var"))
+    y = torch.full((B, OH, OW, C), float("nan"), dtype=dtype, device=dev)
+    rc = lib.xpt_dwconv_bn_relu6_fwd(ptr(x), ptr(w), ptr(gamma), ptr(beta), ptr(mean), ptr(var), EPS, ptr(y), B, H, W, C, stride,
+                                     pt, pl, OH, OW, int(act_in), stream)
+    assert rc == 0, rc
+    chunks = lib.xpt_dwconv_bn_relu6_bwd_chunks(B, OH, OW, C)
+    assert chunks >= 1
+    partials = torch.full((chunks, 11 * C), float("nan"), dtype=torch.float32, device=dev)
+    dx = torch.full((B, H, W, C), float("nan"), dtype=dtype, device=dev) if want_dx else None
+    rc = lib.xpt_dwconv_bn_relu6_bwd(ptr(x), ptr(y), ctypes.c_void_p(dy_dev), dy_pitch, ptr(w), ptr(gamma), ptr(mean), ptr(var), EPS,
+                                     None if dx is None else ptr(dx), ptr(partials), partials.numel(), B, H, W, C, stride, pt, pl,
+                                     OH, OW, int(act_in), stream)
+    assert rc == 0, rc
+    torch.cuda.synchronize()
+    return y, dx, partials
+
+
+def bound_ok(got, ref, rel, what):
+    err = (got.double().cpu() - ref).abs()
+    allowed = rel * ref.abs() + 1e-4 * ref.abs().max()
+    worst = float((err / allowed.clamp_min(1e-300)).max())
+    print(f"  {what}: max |err| {float(err.max()):.3e}, worst err / bound {worst:.3f}")
+    return bool(torch.isfinite(got).all()) and worst <= 1.0
+
+
+def check(lib, dev, shape, act_in, fmt, c, outputs, thorough=True):
+    """One case against its fp64 reference with `outputs` outputs per lane in the forward (forced through the tune knob unless it
+    is what the plan picks by itself); thorough: also the repeat, sliced-dy and dx = NULL runs."""
+    B, H, W, C, stride = shape
+    dtype, rel = FORMATS[fmt]
+    ref = c["ref"]
+    pt, pl, OH, OW = c["geom"]
+    print(f"\n{shape} act_in={act_in} {fmt} outputs/lane={outputs}: y at 0 / inside / at 6 = {c['shares'][0]:.3f} / "
+          f"{c['shares'][1]:.3f} / {c['shares'][2]:.3f}; dy zeroed near the kinks: {c['zeroed']:.4f}")
+    assert min(c["shares"]) >= 0.05, c["shares"]                 # all three branches of the clamp are exercised
+    assert c["zeroed"] <= 0.05, c["zeroed"]
+    if act_in:
+        assert float((c["x"] < 0).double().mean()) > 0.1 and float((c["x"] > 6).double().mean()) > 0.05
+    assert lib.xpt_dwconv_bn_relu6_fwd_outputs(B, OH, OW, C) == outputs           # the forward variant this case runs
+    dy = nhwc(c["dy"], dtype, dev)
+    y, dx, partials = run(lib, dev, fmt, shape, act_in, c, dy.data_ptr(), C)
+    assert bound_ok(y.permute(0, 3, 1, 2), ref["y"], rel, "y")
+    assert bound_ok(dx.permute(0, 3, 1, 2), ref["dx"], rel, "dx")
+    total = partials.double().sum(0).cpu()
+    assert bool(torch.isfinite(partials).all())
+    for what, got, want in (("dw", total[:9 * C].view(C, 1, 3, 3), ref["dw"]), ("dgamma", total[9 * C:10 * C], ref["dgamma"]),
+                            ("dbeta", total[10 * C:], ref["dbeta"])):
+        err = float((got - want).abs().max())
+        print(f"  {what}: max |err| {err:.3e} of max|ref| {float(want.abs().max()):.3e} ({partials.shape[0]} chunks)")
+        assert err <= 1e-4 * float(want.abs().max()), what
+    if not thorough:
+        return
+    # a second run: bit-identical partials (fixed chunk order, no atomics)
+    y2, dx2, partials2 = run(lib, dev, fmt, shape, act_in, c, dy.data_ptr(), C)
+    assert torch.equal(partials, partials2) and torch.equal(dx.view(torch.int16), dx2.view(torch.int16))
+    assert torch.equal(y.view(torch.int16), y2.view(torch.int16))
+    # dy as a channel slice of a wider tensor, read in place: bit for bit the dense result; dx = NULL leaves the partials alone
+    pitch = C + 16
+    wide = torch.full((B, dy.shape[1], dy.shape[2], pitch), float("nan"), dtype=dtype, device=dev)
+    wide[..., 8:8 + C] = dy
+    _, dx3, partials3 = run(lib, dev, fmt, shape, act_in, c, wide.data_ptr() + 16, pitch)
+    assert torch.equal(partials, partials3) and torch.equal(dx.view(torch.int16), dx3.view(torch.int16))
+    _, none, partials4 = run(lib, dev, fmt, shape, act_in, c, dy.data_ptr(), C, want_dx=False)
+    assert none is None and torch.equal(partials, partials4)
+
+
+@pytest.mark.parametrize("outputs", [1, 2, 4])
+@pytest.mark.parametrize("fmt", ["bf16", "fp16"])
+@pytest.mark.parametrize("act_in", [0, 1])
+@pytest.mark.parametrize("shape", SHAPES, ids=lambda s: "x".join(str(v) for v in s))
+def test_depthwise_bn_relu6_forward_and_backward_against_fp64(gpu_device, shape, act_in, fmt, outputs):
+    """Every forward variant (1, 2, 4 neighbouring outputs per lane) on every shape: by themselves these small maps all plan one
+    output per lane, the other two are forced through xpt_dwconv_bn_relu6_tune.  The output widths 7, 5, 3, 3, 3 and 12 are no
+    multiples of 2 / 4 (but 12), so the ragged last group of a row is run at both strides."""
+    import xpt_mde_2021_amd.hip.lib  # noqa: F401  (torch's HIP runtime first)
+    lib = library(fmt)
+    assert lib.xpt_dwconv_bn_relu6_tune(3) == -3
+    assert lib.xpt_dwconv_bn_relu6_tune(0) == 0 and lib.xpt_dwconv_bn_relu6_fwd_outputs(*_out_geom(shape)) == 1
+    assert lib.xpt_dwconv_bn_relu6_tune(outputs) == 0
+    try:
+        check(lib, gpu_device, shape, act_in, fmt, case(shape, bool(act_in), fmt), outputs)
+    finally:
+        assert lib.xpt_dwconv_bn_relu6_tune(0) == 0
+
+
+def _out_geom(shape):
+    B, H, W, C, stride = shape
+    _, _, _, _, OH, OW = same_pads(H, W, stride)
+    return B, OH, OW, C
+
+
+# maps large enough that the plan picks 2 / 4 outputs per lane BY ITSELF (>= 512 workgroups of 256 lanes left), widths ragged
+# against both: the half-resolution stages of the benchmarked workload run these variants
+PLANNED = [((8, 64, 207, 32, 1), 2), ((8, 128, 207, 32, 1), 4)]
+
+
+@pytest.mark.parametrize("shape,outputs", PLANNED, ids=lambda v: "x".join(str(i) for i in v) if isinstance(v, tuple) else str(v))
+def test_forward_variants_the_plan_picks_on_large_maps(gpu_device, shape, outputs):
+    import xpt_mde_2021_amd.hip.lib  # noqa: F401
+    from xpt_mde_2021_amd.hip import lib as xl
+    fmt = xl.half_format()
+    lib = library(fmt)
+    assert lib.xpt_dwconv_bn_relu6_tune(0) == 0
+    check(lib, gpu_device, shape, 1, fmt, case.__wrapped__(shape, True, fmt), outputs, thorough=False)
+
+
+def test_gradients_land_on_their_parameters_through_the_gradient_sink(gpu_device):
+    """Training path: weight, gamma and beta carry `flat_grad` views (as optimizers.FlatParameters sets them), the backward leaves
+    partial rows [C * 9 | C | C] behind and GradSink.flush() adds them through xpt_reduce_partials -- three jobs at offsets 0, 9 C
+    and 10 C.  Each destination is compared with ITS fp64 gradient (gamma's and beta's differ by far more than the bound)."""
+    from xpt_mde_2021_amd.hip import lib as xl, ops
+    from xpt_mde_2021_amd.model.build_model.pretrained_nets import FrozenBatchNorm
+    fmt = xl.half_format()
+    dtype, rel = FORMATS[fmt]
+    shape = (2, 4, 6, 576, 2)
+    B, H, W, C, stride = shape
+    c = case(shape, True, fmt)
+    ref = c["ref"]
+    bn = FrozenBatchNorm(C).to(gpu_device)
+    with torch.no_grad():
+        bn.weight.copy_(c["gamma"]), bn.bias.copy_(c["beta"]), bn.running_mean.copy_(c["mean"]), bn.running_var.copy_(c["var"])
+    weight = torch.nn.Parameter(c["w"].float().to(gpu_device))
+    flat = torch.full((11 * C + 16,), float("nan"), device=gpu_device)             # one flat gradient buffer, three views
+    weight.flat_grad = flat[:9 * C].view(C, 1, 3, 3)
+    bn.weight.flat_grad = flat[9 * C + 8:10 * C + 8]
+    bn.bias.flat_grad = flat[10 * C + 16:]
+    sink = ops.grad_sink
+    assert sink.enabled and not sink.pending
+    x = c["x"].to(dtype).to(gpu_device).contiguous(memory_format=torch.channels_last).requires_grad_(True)
+    y = ops.dwconv_bn_relu6(x, weight, bn, stride, act_in=True, eps=EPS)
+    y.backward(c["dy"].to(dtype).to(gpu_device).contiguous(memory_format=torch.channels_last))
+    assert weight.grad is None and bn.weight.grad is None and bn.bias.grad is None          # deferred, not returned
+    assert len(sink.pending) == 3
+    sink.flush()
+    torch.cuda.synchronize()
+    assert bound_ok(x.grad, ref["dx"], rel, "dx")
+    far = float((ref["dgamma"] - ref["dbeta"]).abs().max())
+    assert far > 1e-2 * float(ref["dgamma"].abs().max())                          # a swap of the two could not pass
+    for what, got, want in (("dw", weight.flat_grad, ref["dw"]), ("dgamma", bn.weight.flat_grad, ref["dgamma"]),
+                            ("dbeta", bn.bias.flat_grad, ref["dbeta"])):
+        err = float((got.double().cpu() - want).abs().max())
+        print(f"  {what} through the sink: max |err| {err:.3e} of max|ref| {float(want.abs().max()):.3e}")
+        assert err <= 1e-4 * float(want.abs().max()), what
+    assert bool(torch.isnan(flat[9 * C:9 * C + 8]).all()) and bool(torch.isnan(flat[10 * C + 8:10 * C + 16]).all())   # nothing beyond
+
+
+def test_autograd_op_equals_the_c_abi_and_the_torch_fallback_path(gpu_device):
+    """hip.ops.dwconv_bn_relu6 on 16-bit CUDA tensors is the kernel pair (same bits as the C ABI calls above); on fp32 CUDA
+    tensors it is the torch arithmetic, which the kernel result matches within the 16-bit bound."""
+    from xpt_mde_2021_amd.hip import lib as xl, ops
+    from xpt_mde_2021_amd.model.build_model.pretrained_nets import FrozenBatchNorm
+    fmt = xl.half_format()
+    dtype, rel = FORMATS[fmt]
+    shape = (2, 6, 10, 24, 2)
+    B, H, W, C, stride = shape
+    c = case(shape, True, fmt)
+    bn = FrozenBatchNorm(C).to(gpu_device)
+    with torch.no_grad():
+        bn.weight.copy_(c["gamma"]), bn.bias.copy_(c["beta"]), bn.running_mean.copy_(c["mean"]), bn.running_var.copy_(c["var"])
+    weight = torch.nn.Parameter(c["w"].float().to(gpu_device))
+    x = c["x"].to(dtype).to(gpu_device).contiguous(memory_format=torch.channels_last).requires_grad_(True)
+    y = ops.dwconv_bn_relu6(x, weight, bn, stride, act_in=True, eps=EPS)
+    dy = c["dy"].to(dtype).to(gpu_device).contiguous(memory_format=torch.channels_last)
+    y.backward(dy)
+    ref = c["ref"]
+    assert y.dtype == dtype and bound_ok(y, ref["y"], rel, "y") and bound_ok(x.grad, ref["dx"], rel, "dx")
+    for what, got, want in (("dw", weight.grad, ref["dw"]), ("dgamma", bn.weight.grad, ref["dgamma"]), ("dbeta", bn.bias.grad, ref["dbeta"])):
+        assert float((got.double().cpu() - want).abs().max()) <= 1e-4 * float(want.abs().max()), what
+    x32 = c["x"].float().to(gpu_device).requires_grad_(True)
+    y32 = ops.dwconv_bn_relu6(x32, weight, bn, stride, act_in=True, eps=EPS)
+    assert y32.dtype == torch.float32 and float((y32.double().cpu() - ref["y"]).abs().max()) <= 1e-4 * 6.0

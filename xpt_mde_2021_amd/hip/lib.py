@@ -211,6 +211,11 @@ SIGNATURES = {
     "xpt_affine_act_bwd_workspace_floats": (_z, [ctypes.c_longlong, _i]),
     "xpt_affine_act_bwd": (_i, [_p, _p, _p, ctypes.c_longlong, _p, _p, _p, _p, _f, _p, _p, _p, _p, _z, ctypes.c_longlong,
                                 _i, _f, _i, _i, _p]),
+    "xpt_dwconv_bn_relu6_fwd": (_i, [_p, _p, _p, _p, _p, _p, _f, _p] + [_i] * 10 + [_p]),
+    "xpt_dwconv_bn_relu6_tune": (_i, [_i]),
+    "xpt_dwconv_bn_relu6_fwd_outputs": (_i, [_i] * 4),
+    "xpt_dwconv_bn_relu6_bwd_chunks": (_i, [_i] * 4),
+    "xpt_dwconv_bn_relu6_bwd": (_i, [_p, _p, _p, ctypes.c_longlong, _p, _p, _p, _p, _f, _p, _p, _z] + [_i] * 10 + [_p]),
 }
 
 

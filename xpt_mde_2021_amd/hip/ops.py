@@ -891,6 +891,102 @@ def multi_depthwise(inputs, weights, relu_in=True, stride=1, pads=None):
     return list(_MultiDepthwise.apply(relu_in, int(stride), tuple(tuple(p) for p in pads), *inputs, *weights))
 
 
+# ------------------------------------------------------------------------------- MobileNetV2 depthwise stage
+def _same_pads3(h, w, stride):
+    """(top, left) zeros and output size of a 3x3 window with TF SAME padding (= keras correct_pad + valid at stride 2)."""
+    if stride == 1:
+        return 1, 1, h, w
+    oh, ow = -(-h // 2), -(-w // 2)
+    return ((oh - 1) * 2 + 3 - h) // 2, ((ow - 1) * 2 + 3 - w) // 2, oh, ow
+
+
+class _DwBnRelu6(torch.autograd.Function):
+    """relu6(BatchNorm(depthwise3x3(a(x)))) in one launch, its whole backward in one more (csrc/xpt_mbconv.hip)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, mean, var, eps, stride, act_in):
+        lib = _lib.load()
+        x = _nhwc(x, "x")
+        B, C, H, W = x.shape
+        w = weight.detach().contiguous()
+        g_, b_ = gamma.detach().contiguous(), beta.detach().contiguous()
+        for name, t, n in (("weight", w, 9 * C), ("gamma", g_, C), ("beta", b_, C), ("mean", mean, C), ("var", var, C)):
+            if t.dtype != torch.float32 or not t.is_cuda or t.numel() != n or not t.is_contiguous():
+                raise _lib.XptHipError(f"dwconv_bn_relu6: {name} must be a contiguous float32 CUDA tensor of {n} elements")
+        pt, pl, OH, OW = _same_pads3(H, W, stride)
+        y = torch.empty((B, C, OH, OW), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        _lib.check(lib.xpt_dwconv_bn_relu6_fwd(_ptr(x), _ptr(w), _ptr(g_), _ptr(b_), _ptr(mean), _ptr(var), float(eps), _ptr(y),
+                                               B, H, W, C, stride, pt, pl, OH, OW, int(act_in), _stream()),
+                   "xpt_dwconv_bn_relu6_fwd")
+        ctx.save_for_backward(x, y, w, g_, mean, var)
+        ctx.cfg = (float(eps), stride, pt, pl, OH, OW, int(act_in), weight.shape)
+        ctx.sink_dst = None
+        if grad_sink.wants(weight) and grad_sink.wants(gamma) and grad_sink.wants(beta):
+            ctx.sink_dst = (weight.flat_grad, gamma.flat_grad, beta.flat_grad)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy_in):
+        lib = _lib.load()
+        x, y, w, gamma, mean, var = ctx.saved_tensors
+        eps, stride, pt, pl, OH, OW, act_in, wshape = ctx.cfg
+        B, C, H, W = x.shape
+        dy, pitch = _rows_with_pitch(dy_in.to(x.dtype))
+        if pitch % 8 or dy.data_ptr() % 16:                      # (a slice the 16-byte loads cannot take in place)
+            dy, pitch = dy.contiguous(memory_format=torch.channels_last), C
+        dx = torch.empty_like(x, memory_format=torch.channels_last) if ctx.needs_input_grad[0] else None
+        nchunk = lib.xpt_dwconv_bn_relu6_bwd_chunks(B, OH, OW, C)
+        row = 11 * C
+        if ctx.sink_dst is not None:
+            ws = grad_sink.partials(ctx.sink_dst[0], "mbconv", nchunk * row)
+        elif torch.cuda.is_current_stream_capturing():
+            # (torch.sum inside a captured step: a memset node this runtime replays wrongly, DESIGN.md section 6)
+            raise _lib.XptHipError("dwconv_bn_relu6 backward without flat-gradient destinations inside a graph capture")
+        else:
+            ws = torch.empty(nchunk * row, dtype=torch.float32, device=x.device)
+        _lib.check(lib.xpt_dwconv_bn_relu6_bwd(_ptr(x), _ptr(y), _ptr(dy), pitch, _ptr(w), _ptr(gamma), _ptr(mean), _ptr(var),
+                                               eps, _ptr(dx), _ptr(ws), ws.numel(), B, H, W, C, stride, pt, pl, OH, OW, act_in,
+                                               _stream()), "xpt_dwconv_bn_relu6_bwd")
+        if ctx.sink_dst is not None:
+            dst_w, dst_g, dst_b = ctx.sink_dst
+            grad_sink.add(dst_w, ws, 0, 9 * C, nchunk, row)
+            grad_sink.add(dst_g, ws, 9 * C, C, nchunk, row)
+            grad_sink.add(dst_b, ws, 10 * C, C, nchunk, row)
+            return dx, None, None, None, None, None, None, None, None
+        tot = ws[:nchunk * row].view(nchunk, row).sum(0)
+        return dx, tot[:9 * C].view(wshape), tot[9 * C:10 * C], tot[10 * C:], None, None, None, None, None
+
+
+def dwconv_bn_relu6(x, weight, bn, stride=1, act_in=False, eps=1e-3):
+    """relu6(bn(depthwise3x3_same(a(x), weight, stride))), a = relu6 when act_in (the activation behind the PRECEDING
+    BatchNorm, whose output x is stored pre-activation): the middle of a MobileNetV2 inverted-residual block.  x NCHW-indexed,
+    weight [C,1,3,3], bn: a module with weight / bias / running_mean / running_var (moving statistics, trainable gamma / beta).
+    16-bit CUDA activations run the gfx950 kernels of csrc/xpt_mbconv.hip (one launch forward, one backward; parameter gradients
+    through the GradSink when the parameters live in flat buffers); host tensors and fp32 / fp64 inputs -- the reference
+    arithmetic of the fp64 checks -- take the torch ops below."""
+    if stride not in (1, 2):
+        raise _lib.XptHipError("dwconv_bn_relu6: stride 1 or 2")
+    if x.is_cuda and x.dtype == _lib.half():
+        return _DwBnRelu6.apply(x, weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(eps), int(stride),
+                                bool(act_in))
+    return dwconv_bn_relu6_torch(x, weight, bn, stride, act_in, eps)
+
+
+def dwconv_bn_relu6_torch(x, weight, bn, stride=1, act_in=False, eps=1e-3):
+    """The same stage in torch ops, in x's dtype: the host / fp32 / fp64 path of dwconv_bn_relu6 and the yardstick its kernels are
+    measured against (tests/test_mobilenet_v2_gpu.py)."""
+    import torch.nn.functional as F
+    a = F.relu6(x) if act_in else x                    # (hardtanh: no gradient at exactly 0 and 6, as tf.nn.relu6)
+    H, W = x.shape[2:]
+    pt, pl, OH, OW = _same_pads3(H, W, stride)
+    if stride == 2:                                    # ZeroPadding2D(correct_pad) + "valid"
+        a = F.pad(a, (pl, (OW - 1) * 2 + 3 - W - pl, pt, (OH - 1) * 2 + 3 - H - pt))
+    u = F.conv2d(a, weight.to(a.dtype), None, stride, 1 if stride == 1 else 0, 1, x.shape[1])
+    y = F.batch_norm(u, bn.running_mean.to(a.dtype), bn.running_var.to(a.dtype), bn.weight.to(a.dtype), bn.bias.to(a.dtype),
+                     False, 0.0, eps)
+    return F.relu6(y)
+
+
 # ------------------------------------------------------------------------------- per-channel conv epilogues
 def _rows_with_pitch(t):
     """NCHW-indexed tensor -> (tensor, row pitch in elements) readable as [B*H*W rows, C] with unit channel stride:

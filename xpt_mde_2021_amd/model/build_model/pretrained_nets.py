@@ -1463,7 +1463,8 @@ def load_keras_weights(encoder, weights):
 class PretrainedModel:
     """pretrained_nets.py:11-117 interface: PretrainedModel(net_name, use_pt_weight).encoder() builds the module
     whose forward is the reference's `.encode(input_image)`."""
-    SUPPORTED = ("NASNetMobile",)
+    SUPPORTED = ("NASNetMobile", "MobileNetV2")          # (MobileNetV2: build_model/mobilenet_v2.py)
+    WEIGHT_ENV = {"NASNetMobile": "XPT_NASNET_WEIGHTS", "MobileNetV2": "XPT_MOBILENETV2_WEIGHTS"}
 
     def __init__(self, net_name, use_pt_weight):
         if net_name not in self.SUPPORTED:
@@ -1473,14 +1474,21 @@ class PretrainedModel:
         if use_pt_weight:
             # weights="imagenet" (pretrained_nets.py:23) downloads from the Keras storage bucket; offline the user
             # supplies the same variables as a file (one-line export where Keras is installed)
-            self.weight_file = __import__("os").environ.get("XPT_NASNET_WEIGHTS", "")
+            env = self.WEIGHT_ENV[net_name]
+            self.weight_file = __import__("os").environ.get(env, "")
             if not self.weight_file:
                 raise WrongInputException("ImageNet weights (Keras storage bucket download, pretrained_nets.py:23) are not "
-                                          "obtainable offline: point XPT_NASNET_WEIGHTS at an .npz / .h5 of the Keras "
-                                          "NASNetMobile(include_top=False) variables, or set opts.PRETRAINED_WEIGHT = False")
+                                          f"obtainable offline: point {env} at an .npz / .h5 of the Keras "
+                                          f"{net_name}(include_top=False) variables, or set opts.PRETRAINED_WEIGHT = False")
         self.net_name = net_name
 
     def encoder(self):
+        if self.net_name == "MobileNetV2":
+            from . import mobilenet_v2 as mv2          # (imports this module)
+            net = mv2.MobileNetV2Encoder()
+            if self.weight_file:
+                mv2.load_keras_weights(net, self.weight_file)
+            return net
         net = NASNetMobileEncoder()
         if self.weight_file:
             load_keras_weights(net, self.weight_file)
