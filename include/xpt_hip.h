@@ -776,6 +776,65 @@ int xpt_dwconv_bn_relu6_bwd(const void* x, const void* y, const void* dy, long l
                             size_t partial_floats, int B, int H, int W, int C, int stride, int pad_t, int pad_l, int OH, int OW,
                             int act_in, void* stream);
 
+/* ------------------------------------------------------------------ EfficientNet MBConv middle (csrc/xpt_effconv.hip)
+ * DepthwiseConv2D k x k -> BatchNormalization (moving statistics) -> swish -> squeeze-and-excite: `block` of
+ * tf.keras.applications.EfficientNetB0 .. B7 (include_top=False) between its expand and project convolutions, the backbones
+ * model/build_model/pretrained_nets.py:11-117 instantiates for config-example.py's JOINT_NET "depth" default and RIGID_EF0 / EF3 /
+ * EF5 / EF7.  sw(v) = v sigma(v), sw'(v) = sigma(v) (1 + v (1 - sigma(v))).  x [B,H,W,C], v / z / dz [B,OH,OW,C] NHWC in the
+ * 16-bit format of the build; parameters, pooled values, gates and accumulation fp32.  Common to all entries: C % 8 == 0 and
+ * 16-byte aligned pointers where stated (else XPT_ERR_ARG / XPT_ERR_SHAPE before any launch), tensors below 2 GiB, no atomics and
+ * a fixed summation order (same bits on every call).
+ *
+ * One plan serves every sum over pixels: xpt_dwconv_bn_swish_chunks(B, OH, OW, C) = B * chunks_per_image rows of a partial
+ * matrix, row b * chunks_per_image + i belonging to image b alone (0 for sizes the kernels refuse).  The forward has a single
+ * variant, so there is no _tune / _outputs pair.
+ *
+ * xpt_dwconv_bn_swish_fwd (DepthwiseConv2D + BatchNormalization of `block`; the Activation('swish') BEHIND it is applied by
+ * its consumers): a(v) = sw(v) when act_in (the swish of the PRECEDING BatchNorm, stored pre-activation), else v;
+ *   u = sum_{ky,kx<k} w[c,ky,kx] a(x[b, oy stride + ky - pad_t, ox stride + kx - pad_l, c])   (zero outside the input)
+ *   v = s[c] u + t[c],  s = gamma rsqrt(var + eps),  t = beta - mean s                         (v is what is stored)
+ *   pool_partials[row][c] = sum over the row's pixels of sw(v), from the fp32 v before the store rounds it
+ * k in {3, 5}, stride in {1, 2}, pad_t / pad_l in [0, k/2] with the centre of every window inside the input (TF SAME padding:
+ * pad_t = ((OH - 1) stride + k - H) / 2 = keras correct_pad + valid at stride 2); w [C][k][k], x / v / w 16-byte aligned;
+ * pool_floats >= chunks * C (else XPT_ERR_WORKSPACE). */
+int xpt_dwconv_bn_swish_chunks(int B, int OH, int OW, int C);
+int xpt_dwconv_bn_swish_fwd(const void* x, const float* w, const float* gamma, const float* beta, const float* mean,
+                            const float* var, float eps, void* v, float* pool_partials, size_t pool_floats, int B, int H, int W,
+                            int C, int k, int stride, int pad_t, int pad_l, int OH, int OW, int act_in, void* stream);
+/* GlobalAveragePooling2D -> se_reduce (Conv2D 1x1, bias, swish) -> se_expand (Conv2D 1x1, bias, sigmoid) of `block`:
+ *   p[b,c] = (sum of image b's chunks_per_image partial rows, in row order) / HW
+ *   r = W_r p + b_r (S values),  q = sw(r),  e = W_e q + b_e,  gate = sigma(e)
+ * w_reduce [S][C] and w_expand [C][S] row-major (the [out][in][1][1] convolution kernels as they lie in memory -- the issue's
+ * sketch had them transposed); outputs p [B][C], r [B][S] (kept for the backward), gate [B][C] (16-byte aligned).  Any S >= 1
+ * with C + S <= 12288. */
+int xpt_se_excite_fwd(const float* pool_partials, int chunks_per_image, int HW, const float* w_reduce, const float* b_reduce,
+                      const float* w_expand, const float* b_expand, float* p, float* r, float* gate, int B, int C, int S,
+                      void* stream);
+/* Activation('swish') + multiply of `block`: z = sw(v) gate[b,c] (16-bit), the input of the project convolution. */
+int xpt_se_scale_fwd(const void* v, const float* gate, void* z, int B, int OH, int OW, int C, void* stream);
+/* dgate[b,c] = sum_hw dz sw(v) ([B][C] fp32): partial rows (partial_floats >= chunks * C) and their fixed-order finish, two
+ * launches in this call.  dz is read with a pixel pitch (elements, % 8 == 0): a channel slice is consumed in place. */
+int xpt_se_scale_bwd_reduce(const void* v, const void* dz, long long dz_pitch, float* partials, size_t partial_floats,
+                            float* dgate, int B, int OH, int OW, int C, void* stream);
+/* Backward of xpt_se_excite_fwd, ONE launch: de = dgate g (1 - g); dw_expand [C][S] = sum_b de q, db_expand [C] = sum_b de,
+ * dq = W_e^T de, dr = dq sw'(r), dw_reduce [S][C] = sum_b dr p, db_reduce [S] = sum_b dr, dp [B][C] = W_r^T dr (the gradient
+ * w.r.t. the pooled mean; 16-byte aligned).  The four parameter gradients are complete sums over the batch, in image order
+ * (a GradSink job of one row each).  2 B S <= 12288. */
+int xpt_se_excite_bwd(const float* dgate, const float* gate, const float* p, const float* r, const float* w_reduce,
+                      const float* w_expand, float* dw_reduce, float* db_reduce, float* dw_expand, float* db_expand, float* dp,
+                      int B, int C, int S, void* stream);
+/* The whole depthwise backward in ONE launch.  gz = sw'(v) (dz gate[b,c] + dp[b,c] / (OH OW)) is formed on load from the stored
+ * v (both paths into v: through the multiply and through the pool); dx = a'(x) s sum_k w_k gz (a' = sw' when act_in: the
+ * gradient w.r.t. the preceding BatchNorm's output); dx may be NULL; dz with a pixel pitch as above.  partials: chunks rows of
+ * (k k + 2) C floats in parameter units (rows simply add): with G[c,t] = sum gz a(x)[tap t] a row is [C][k k] s G (dL/dw) |
+ * [C] rsqrt(var + eps) (sum_t w_t G_t - mean sum gz) (dL/dgamma, as xpt_dwconv_bn_relu6_bwd) | [C] sum gz (dL/dbeta) -- three
+ * contiguous pieces, each a job of xpt_reduce_partials with stride (k k + 2) C.  Takes the moving mean, as the MobileNetV2
+ * stage does. */
+int xpt_dwconv_bn_swish_bwd(const void* x, const void* v, const void* dz, long long dz_pitch, const float* gate, const float* dp,
+                            const float* w, const float* gamma, const float* mean, const float* var, float eps, void* dx,
+                            float* partials, size_t partial_floats, int B, int H, int W, int C, int k, int stride, int pad_t,
+                            int pad_l, int OH, int OW, int act_in, void* stream);
+
 /* ------------------------------------------------------------------ captured-step audit (no reference counterpart)
  * Node census of a captured hipGraph (hipGraph_t as torch.cuda.CUDAGraph(keep_graph=True).raw_cuda_graph() hands it out),
  * child graphs included: counts[6] = kernel, memcpy, memset, host, other nodes, total.  The trainers that replace the

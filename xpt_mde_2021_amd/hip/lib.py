@@ -216,6 +216,13 @@ SIGNATURES = {
     "xpt_dwconv_bn_relu6_fwd_outputs": (_i, [_i] * 4),
     "xpt_dwconv_bn_relu6_bwd_chunks": (_i, [_i] * 4),
     "xpt_dwconv_bn_relu6_bwd": (_i, [_p, _p, _p, ctypes.c_longlong, _p, _p, _p, _p, _f, _p, _p, _z] + [_i] * 10 + [_p]),
+    "xpt_dwconv_bn_swish_chunks": (_i, [_i] * 4),
+    "xpt_dwconv_bn_swish_fwd": (_i, [_p, _p, _p, _p, _p, _p, _f, _p, _p, _z] + [_i] * 11 + [_p]),
+    "xpt_se_excite_fwd": (_i, [_p, _i, _i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _p]),
+    "xpt_se_scale_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
+    "xpt_se_scale_bwd_reduce": (_i, [_p, _p, ctypes.c_longlong, _p, _z, _p, _i, _i, _i, _i, _p]),
+    "xpt_se_excite_bwd": (_i, [_p] * 11 + [_i, _i, _i, _p]),
+    "xpt_dwconv_bn_swish_bwd": (_i, [_p, _p, _p, ctypes.c_longlong, _p, _p, _p, _p, _p, _p, _f, _p, _p, _z] + [_i] * 11 + [_p]),
 }
 
 

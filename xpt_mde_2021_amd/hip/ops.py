@@ -987,6 +987,150 @@ def dwconv_bn_relu6_torch(x, weight, bn, stride=1, act_in=False, eps=1e-3):
     return F.relu6(y)
 
 
+# ------------------------------------------------------------------------------- EfficientNet MBConv middle
+def _same_pads(h, w, k, stride):
+    """(top, left) zeros and output size of a k x k window with TF SAME padding (= keras correct_pad + valid at stride 2)."""
+    oh, ow = -(-h // stride), -(-w // stride)
+    return max((oh - 1) * stride + k - h, 0) // 2, max((ow - 1) * stride + k - w, 0) // 2, oh, ow
+
+
+class _MbconvSE(torch.autograd.Function):
+    """depthwise k x k -> BatchNorm -> swish -> squeeze-and-excite -> multiply on the kernels of csrc/xpt_effconv.hip: three
+    launches forward (depthwise stage with pool partials, excite, scale), four backward (dL/dgate rows and their finish, excite
+    backward, depthwise backward)."""
+
+    @staticmethod
+    def forward(ctx, x, weight, gamma, beta, mean, var, wr, br, we, be, eps, k, stride, act_in):
+        lib = _lib.load()
+        x = _nhwc(x, "x")
+        B, C, H, W = x.shape
+        S = wr.shape[0]
+        f32 = lambda t: t.detach().contiguous()                 # noqa: E731
+        w, g_, b_, wr_, br_, we_, be_ = (f32(t) for t in (weight, gamma, beta, wr, br, we, be))
+        for name, t, n in (("dw_weight", w, k * k * C), ("gamma", g_, C), ("beta", b_, C), ("mean", mean, C), ("var", var, C),
+                           ("se_reduce_w", wr_, S * C), ("se_reduce_b", br_, S), ("se_expand_w", we_, C * S), ("se_expand_b", be_, C)):
+            if t.dtype != torch.float32 or not t.is_cuda or t.numel() != n or not t.is_contiguous():
+                raise _lib.XptHipError(f"mbconv_se: {name} must be a contiguous float32 CUDA tensor of {n} elements")
+        pt, pl, OH, OW = _same_pads(H, W, k, stride)
+        nchunk = lib.xpt_dwconv_bn_swish_chunks(B, OH, OW, C)
+        if nchunk <= 0:
+            raise _lib.XptHipError(f"mbconv_se: no plan for a {B} x {OH} x {OW} x {C} map (channels must be a multiple of 8)")
+        dev = x.device
+        v = torch.empty((B, C, OH, OW), dtype=x.dtype, device=dev, memory_format=torch.channels_last)
+        z = torch.empty_like(v, memory_format=torch.channels_last)
+        pool = torch.empty(nchunk * C, dtype=torch.float32, device=dev)
+        p, gate = torch.empty((B, C), dtype=torch.float32, device=dev), torch.empty((B, C), dtype=torch.float32, device=dev)
+        r = torch.empty((B, S), dtype=torch.float32, device=dev)
+        s = _stream()
+        _lib.check(lib.xpt_dwconv_bn_swish_fwd(_ptr(x), _ptr(w), _ptr(g_), _ptr(b_), _ptr(mean), _ptr(var), float(eps), _ptr(v),
+                                               _ptr(pool), pool.numel(), B, H, W, C, k, stride, pt, pl, OH, OW, int(act_in), s),
+                   "xpt_dwconv_bn_swish_fwd")
+        _lib.check(lib.xpt_se_excite_fwd(_ptr(pool), nchunk // B, OH * OW, _ptr(wr_), _ptr(br_), _ptr(we_), _ptr(be_), _ptr(p),
+                                         _ptr(r), _ptr(gate), B, C, S, s), "xpt_se_excite_fwd")
+        _lib.check(lib.xpt_se_scale_fwd(_ptr(v), _ptr(gate), _ptr(z), B, OH, OW, C, s), "xpt_se_scale_fwd")
+        ctx.save_for_backward(x, v, gate, p, r, w, g_, mean, var, wr_, we_)
+        ctx.cfg = (float(eps), k, stride, pt, pl, OH, OW, int(act_in), S, nchunk)
+        ctx.shapes = (weight.shape, wr.shape, we.shape)
+        params = (weight, gamma, beta, wr, br, we, be)
+        ctx.sink_dst = tuple(t.flat_grad for t in params) if all(grad_sink.wants(t) for t in params) else None
+        return z
+
+    @staticmethod
+    def backward(ctx, dz_in):
+        import ctypes
+        lib = _lib.load()
+        x, v, gate, p, r, w, gamma, mean, var, wr, we = ctx.saved_tensors
+        eps, k, stride, pt, pl, OH, OW, act_in, S, nchunk = ctx.cfg
+        B, C, H, W = x.shape
+        dev = x.device
+        dz, pitch = _rows_with_pitch(dz_in.to(x.dtype))
+        if pitch % 8 or dz.data_ptr() % 16:                      # (a slice the 16-byte loads cannot take in place)
+            dz, pitch = dz.contiguous(memory_format=torch.channels_last), C
+        row = (k * k + 2) * C
+        nse = 2 * S * C + S + C                                  # [S C dW_r | S db_r | C S dW_e | C db_e]
+        if ctx.sink_dst is not None:
+            ws = grad_sink.partials(ctx.sink_dst[0], "effconv", nchunk * row)
+            se = grad_sink.partials(ctx.sink_dst[3], "effconv_se", nse)
+        elif torch.cuda.is_current_stream_capturing():
+            # (torch.sum inside a captured step: a memset node this runtime replays wrongly, DESIGN.md section 6)
+            raise _lib.XptHipError("mbconv_se backward without flat-gradient destinations inside a graph capture")
+        else:
+            ws = torch.empty(nchunk * row, dtype=torch.float32, device=dev)
+            se = torch.empty(nse, dtype=torch.float32, device=dev)
+        rows = torch.empty(nchunk * C, dtype=torch.float32, device=dev)
+        dgate, dp = torch.empty((B, C), dtype=torch.float32, device=dev), torch.empty((B, C), dtype=torch.float32, device=dev)
+        dx = torch.empty_like(x, memory_format=torch.channels_last) if ctx.needs_input_grad[0] else None
+        s = _stream()
+        o_wr, o_br, o_we, o_be = 0, S * C, S * C + S, 2 * S * C + S
+        at = lambda off: ctypes.c_void_p(se.data_ptr() + 4 * off)           # noqa: E731
+        _lib.check(lib.xpt_se_scale_bwd_reduce(_ptr(v), _ptr(dz), pitch, _ptr(rows), rows.numel(), _ptr(dgate), B, OH, OW, C, s),
+                   "xpt_se_scale_bwd_reduce")
+        _lib.check(lib.xpt_se_excite_bwd(_ptr(dgate), _ptr(gate), _ptr(p), _ptr(r), _ptr(wr), _ptr(we), at(o_wr), at(o_br),
+                                         at(o_we), at(o_be), _ptr(dp), B, C, S, s), "xpt_se_excite_bwd")
+        _lib.check(lib.xpt_dwconv_bn_swish_bwd(_ptr(x), _ptr(v), _ptr(dz), pitch, _ptr(gate), _ptr(dp), _ptr(w), _ptr(gamma),
+                                               _ptr(mean), _ptr(var), eps, _ptr(dx), _ptr(ws), ws.numel(), B, H, W, C, k, stride,
+                                               pt, pl, OH, OW, act_in, s), "xpt_dwconv_bn_swish_bwd")
+        tail = (None,) * 4
+        if ctx.sink_dst is not None:
+            d_w, d_g, d_b, d_wr, d_br, d_we, d_be = ctx.sink_dst
+            grad_sink.add(d_w, ws, 0, k * k * C, nchunk, row)
+            grad_sink.add(d_g, ws, k * k * C, C, nchunk, row)
+            grad_sink.add(d_b, ws, (k * k + 1) * C, C, nchunk, row)
+            grad_sink.add(d_wr, se, o_wr, S * C, 1, nse)
+            grad_sink.add(d_br, se, o_br, S, 1, nse)
+            grad_sink.add(d_we, se, o_we, C * S, 1, nse)
+            grad_sink.add(d_be, se, o_be, C, 1, nse)
+            return (dx,) + (None,) * 9 + tail
+        wshape, wrshape, weshape = ctx.shapes
+        tot = ws.view(nchunk, row).sum(0)
+        return (dx, tot[:k * k * C].view(wshape), tot[k * k * C:(k * k + 1) * C], tot[(k * k + 1) * C:], None, None,
+                se[o_wr:o_br].view(wrshape), se[o_br:o_we], se[o_we:o_be].view(weshape), se[o_be:]) + tail
+
+
+def mbconv_se(h, dw_weight, dw_bn, se_reduce_w, se_reduce_b, se_expand_w, se_expand_b, k, stride, act_in=True, eps=1e-3):
+    """z = sw(v) * sigmoid(W_e sw(W_r mean_hw sw(v) + b_r) + b_e) with v = dw_bn(depthwise_kxk_same(a(h), dw_weight, stride)),
+    sw = swish, a = swish when act_in (the activation behind the PRECEDING BatchNorm, whose output h is stored pre-activation):
+    the middle of an EfficientNet MBConv block, between its expand and project convolutions.  h NCHW-indexed, dw_weight [C,1,k,k],
+    dw_bn a module with weight / bias / running_mean / running_var (moving statistics, trainable gamma / beta), se_reduce_w
+    [S,C,1,1], se_expand_w [C,S,1,1] with their biases.  16-bit CUDA activations run the gfx950 kernels of csrc/xpt_effconv.hip
+    (parameter gradients through the GradSink when the parameters live in flat buffers; inside a graph capture anything else
+    raises); host tensors and fp32 / fp64 inputs take mbconv_se_torch."""
+    if k not in (3, 5) or stride not in (1, 2):
+        raise _lib.XptHipError("mbconv_se: k in (3, 5), stride 1 or 2")
+    if h.is_cuda and h.dtype == _lib.half():
+        return _MbconvSE.apply(h, dw_weight, dw_bn.weight, dw_bn.bias, dw_bn.running_mean, dw_bn.running_var, se_reduce_w,
+                               se_reduce_b, se_expand_w, se_expand_b, float(eps), int(k), int(stride), bool(act_in))
+    return mbconv_se_torch(h, dw_weight, dw_bn, se_reduce_w, se_reduce_b, se_expand_w, se_expand_b, k, stride, act_in, eps)
+
+
+def mbconv_se_torch(h, dw_weight, dw_bn, se_reduce_w, se_reduce_b, se_expand_w, se_expand_b, k, stride, act_in=True, eps=1e-3):
+    """The same stage in torch ops, in h's dtype: the host / fp32 / fp64 path of mbconv_se and the yardstick its kernels are
+    measured against (tests/test_efficientnet_gpu.py).  Elementwise ops, slices and two matrix products only -- no library
+    convolution or BatchNorm call, so running it leaves MIOpen's solver search and its databases alone.  Operands are in h's
+    dtype; the window sum and the BatchNorm are evaluated in fp32 for 16-bit inputs and rounded once each, as a library
+    convolution and BatchNorm would."""
+    import torch.nn.functional as F
+    dt = h.dtype
+    acc = torch.float32 if dt in (torch.float16, torch.bfloat16) else dt
+    to = lambda t: t.to(dt).to(acc).view(1, -1, 1, 1)       # noqa: E731  (a per-channel operand, rounded to h's dtype)
+    a = F.silu(h) if act_in else h
+    B, C, H, W = h.shape
+    pt, pl, OH, OW = _same_pads(H, W, k, stride)
+    a = F.pad(a, (pl, max((OW - 1) * stride + k - W, 0) - pl, pt, max((OH - 1) * stride + k - H, 0) - pt)).to(acc)
+    u = None
+    for i in range(k):
+        for j in range(k):
+            tap = a[:, :, i:i + (OH - 1) * stride + 1:stride, j:j + (OW - 1) * stride + 1:stride] * to(dw_weight[:, 0, i, j])
+            u = tap if u is None else u + tap
+    u = u.to(dt).to(acc)
+    scale = to(dw_bn.weight) * torch.rsqrt(to(dw_bn.running_var) + eps)
+    v = ((u - to(dw_bn.running_mean)) * scale + to(dw_bn.bias)).to(dt)
+    y = F.silu(v)
+    q = F.silu(F.linear(y.mean((2, 3)), se_reduce_w.to(dt).flatten(1), se_reduce_b.to(dt)))
+    gate = torch.sigmoid(F.linear(q, se_expand_w.to(dt).flatten(1), se_expand_b.to(dt)))
+    return y * gate.view(B, C, 1, 1)
+
+
 # ------------------------------------------------------------------------------- per-channel conv epilogues
 def _rows_with_pitch(t):
     """NCHW-indexed tensor -> (tensor, row pitch in elements) readable as [B*H*W rows, C] with unit channel stride:

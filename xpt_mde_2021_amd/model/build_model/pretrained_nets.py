@@ -1463,8 +1463,11 @@ def load_keras_weights(encoder, weights):
 class PretrainedModel:
     """pretrained_nets.py:11-117 interface: PretrainedModel(net_name, use_pt_weight).encoder() builds the module
     whose forward is the reference's `.encode(input_image)`."""
-    SUPPORTED = ("NASNetMobile", "MobileNetV2")          # (MobileNetV2: build_model/mobilenet_v2.py)
-    WEIGHT_ENV = {"NASNetMobile": "XPT_NASNET_WEIGHTS", "MobileNetV2": "XPT_MOBILENETV2_WEIGHTS"}
+    # (MobileNetV2: build_model/mobilenet_v2.py; EfficientNetB0 / B3 / B5 / B7: build_model/efficientnet.py)
+    SUPPORTED = ("NASNetMobile", "MobileNetV2", "EfficientNetB0", "EfficientNetB3", "EfficientNetB5", "EfficientNetB7")
+    WEIGHT_ENV = {"NASNetMobile": "XPT_NASNET_WEIGHTS", "MobileNetV2": "XPT_MOBILENETV2_WEIGHTS",
+                  "EfficientNetB0": "XPT_EFFICIENTNETB0_WEIGHTS", "EfficientNetB3": "XPT_EFFICIENTNETB3_WEIGHTS",
+                  "EfficientNetB5": "XPT_EFFICIENTNETB5_WEIGHTS", "EfficientNetB7": "XPT_EFFICIENTNETB7_WEIGHTS"}
 
     def __init__(self, net_name, use_pt_weight):
         if net_name not in self.SUPPORTED:
@@ -1488,6 +1491,12 @@ class PretrainedModel:
             net = mv2.MobileNetV2Encoder()
             if self.weight_file:
                 mv2.load_keras_weights(net, self.weight_file)
+            return net
+        if self.net_name.startswith("EfficientNet"):
+            from . import efficientnet as eff          # (imports this module)
+            net = eff.EfficientNetEncoder(self.net_name)
+            if self.weight_file:
+                eff.load_keras_weights(net, self.weight_file)
             return net
         net = NASNetMobileEncoder()
         if self.weight_file:
