@@ -835,6 +835,51 @@ int xpt_dwconv_bn_swish_bwd(const void* x, const void* v, const void* dz, long l
                             float* partials, size_t partial_floats, int B, int H, int W, int C, int k, int stride, int pad_t,
                             int pad_l, int OH, int OW, int act_in, void* stream);
 
+/* ------------------------------------------------------------------ ResNet50V2 residual junction and pool1 (csrc/xpt_resnet.hip)
+ * `block2` / `stack2` of tf.keras.applications.resnet_v2.ResNet50V2(include_top=False), one of the backbones
+ * model/build_model/pretrained_nets.py:31-101 instantiates.  Activations NHWC in the 16-bit format of the build, parameters and
+ * accumulation fp32.  K, N (and sc_k) multiples of 8, every activation / weight pointer 16-byte aligned, M < 2^31 (else
+ * XPT_ERR_SHAPE / XPT_ERR_ARG before any launch); no atomics, fixed summation order.
+ *
+ * xpt_res_join_fwd replaces, in ONE launch, `<name>_3_conv` (Conv2D 1x1 + bias), the shortcut and `<name>_out` (Add) of one
+ * block and `<next>_preact_bn` + `<next>_preact_relu` of the following block (`post_bn` + `post_relu` after conv5_block3):
+ *   out[m,n] = sum_k h[m,k] w3[n,k] + b3[n] + S[m,n]                          (rounded to 16 bits, stored)
+ *   pre[m,n] = relu(out[m,n] s[n] + t[n]),  s = gamma rsqrt(var + eps),  t = beta - mean s   (from the ROUNDED out)
+ * S is one of
+ *   shortcut[m, n]                               stride 1: the block input (plain block);
+ *   shortcut[(b IH + 2 oy) IW + 2 ox, n]         stride 2, m = (b OH + oy) OW + ox: `MaxPooling2D(1, strides=2)` of the block input
+ *                                                (the LAST block of a stack); needs 2 (OH - 1) < IH, 2 (OW - 1) < IW;
+ *   sum_k sc_x[m,k] sc_w[n,k] + sc_b[n]          `<name>_0_conv` of the pre-activated block input, a second GEMM into the same
+ *                                                accumulator (shortcut NULL; sc_x [M, sc_k] with pixel pitch sc_pitch);
+ *   0                                            (shortcut and sc_x NULL).
+ * h [M,K] with pixel pitch hpitch (elements, % 8 == 0), w3 [N,K] / sc_w [N,sc_k] dense, b3 / sc_b may be NULL, out / pre / shortcut
+ * dense.
+ *
+ * xpt_res_join_bwd, ONE streaming launch: with mask = [out s + t > 0] recomputed from the stored out by the forward's expression,
+ *   g[m,n] = g_out_next[m,n] + g_pre[m,n] mask s[n]          (16 bits: the gradient at `out` -- input of _3_conv's data- and
+ *                                                             weight-gradient GEMMs and the gradient of an identity shortcut)
+ *   g_shortcut (stride 2 only, dense [B IH IW, N], OH = ceil(IH / 2), OW = ceil(IW / 2)): g at the pixels (2 oy, 2 ox), zero at
+ *     every other pixel (all pixels are written; NULL for stride 1)
+ *   partials: xpt_res_join_bwd_blocks(M, N) (<= 256) rows of 3 N floats: [N] sum_m g (db3, of the ROUNDED g) | [N] sum_m g_pre mask
+ *     (dbeta) | [N] sum_m g_pre mask (out - mean) rsqrt(var + eps) (dgamma) -- rows simply add: three jobs of
+ *     xpt_reduce_partials with stride 3 N.
+ * g_out_next / g_pre may be NULL (no gradient from that side); all tensors dense [M,N]. */
+int xpt_res_join_fwd(const void* h, long long hpitch, const void* w3, const float* b3, const void* sc_x, long long sc_pitch,
+                     const void* sc_w, const float* sc_b, int sc_k, const void* shortcut, const float* gamma, const float* beta,
+                     const float* mean, const float* var, float eps, void* out, void* pre, long long M, int K, int N, int stride,
+                     int OH, int OW, int IH, int IW, void* stream);
+int xpt_res_join_bwd_blocks(long long M, int N);
+int xpt_res_join_bwd(const void* g_out_next, const void* g_pre, const void* out, const float* gamma, const float* beta,
+                     const float* mean, const float* var, float eps, void* g, void* g_shortcut, float* partials,
+                     size_t partial_floats, long long M, int N, int stride, int OH, int OW, int IH, int IW, void* stream);
+/* `pool1_pad` (ZeroPadding2D(1)) + `pool1_pool` (MaxPooling2D(3, strides=2)): the padding holds 0.0 and takes part in the max
+ * (the conv1_conv output is signed: a border window of negative values pools to 0).  x [B,H,W,C] -> y [B,OH,OW,C],
+ * OH = (H - 1) / 2 + 1, C % 8 == 0.  TIE RULE: the FIRST maximal tap in row-major window order wins, padded taps included;
+ * idx [B,OH,OW,C] bytes records it (0..8).  Backward: dx[pixel] = sum (window order, fp32) of dy over the windows whose recorded
+ * tap is that pixel; a window won by a padded tap passes no gradient. */
+int xpt_maxpool3s2_zero_fwd(const void* x, void* y, void* idx, int B, int H, int W, int C, int OH, int OW, void* stream);
+int xpt_maxpool3s2_zero_bwd(const void* dy, const void* idx, void* dx, int B, int H, int W, int C, int OH, int OW, void* stream);
+
 /* ------------------------------------------------------------------ captured-step audit (no reference counterpart)
  * Node census of a captured hipGraph (hipGraph_t as torch.cuda.CUDAGraph(keep_graph=True).raw_cuda_graph() hands it out),
  * child graphs included: counts[6] = kernel, memcpy, memset, host, other nodes, total.  The trainers that replace the

@@ -3,10 +3,11 @@
 (one GPU, batch 8, snippets 5 x 128 x 416, bf16, graph mode, synthetic data -- the trainer
 is built the way bench.py builds it).  bench.py measures the flagship (NASNet-Mobile) and is not edited for this.
 
-    python tools/bench_backbone.py [MobileNetV2|EfficientNetB0|NASNetMobile] [--steps 200] [--warmup 20]
+    python tools/bench_backbone.py [MobileNetV2|EfficientNetB0|ResNet50V2|NASNetMobile] [--steps 200] [--warmup 20]
 
 Prints one JSON line; with XPT_BENCH_DW=1 also the device time of every depthwise-stage launch (replayed back to back from a
-captured graph, as tools/hot_replay.py does) against its algorithmic bytes at 8 TB/s."""
+captured graph, as tools/hot_replay.py does) against its algorithmic bytes at 8 TB/s; with XPT_BENCH_JUNCTION=1 (ResNet50V2) the
+residual junction's forward and backward launch at the four stack widths beside the composed torch-op twin, same method."""
 import argparse
 import json
 import os
@@ -88,6 +89,68 @@ def depthwise_stage_floor(dev, batch, height, width, repeats=20, rounds=10):
     return {"stages": rows, "total": {k: (round(v, 2) if isinstance(v, float) else v) for k, v in tot.items()}}
 
 
+def junction_hot_replay(dev, batch, height, width, repeats=20, rounds=10):
+    """The residual junction (csrc/xpt_resnet.hip) at the four stack widths of ResNet50V2 for this input size, plain shortcut:
+    device time per call of the fused forward launch, of the composed forward (hip.ops.res_join_torch: library GEMM plus
+    element-wise launches, same 16-bit dtype) and of the junction's streaming backward launch.  Each is issued `repeats` times
+    back to back inside one captured hipGraph, the graph replayed `rounds` times between two HIP events (tools/hot_replay.py's
+    method: hot caches, launch floor included, no host in the way)."""
+    import ctypes
+    from xpt_mde_2021_amd.hip import lib as xl, ops
+    from xpt_mde_2021_amd.model.build_model import resnet_v2 as rn2
+    lib = xl.load()
+    P = lambda t: ctypes.c_void_p(t.data_ptr())                      # noqa: E731
+
+    def graph_time(launch):
+        launch()
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for _ in range(repeats):
+                launch()
+        g.replay()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(rounds):
+            g.replay()
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1000.0 / (rounds * repeats)
+
+    rows, scale = [], 4
+    for K, _, stride1 in rn2.STACKS:
+        N, h, w = 4 * K, height // scale, width // scale
+        M = batch * h * w
+        x = torch.randn(batch, K, h, w, device=dev).relu().to(xl.half()).contiguous(memory_format=torch.channels_last)
+        sc = torch.randn(batch, N, h, w, device=dev).to(xl.half()).contiguous(memory_format=torch.channels_last)
+        w3 = (torch.randn(N, K, 1, 1, device=dev) / K ** 0.5)
+        w3h = w3.to(xl.half()).reshape(N, K).contiguous()
+        b3 = 0.1 * torch.randn(N, device=dev)
+        bn = rn2.ResBatchNorm(N).to(dev)
+        out, pre, g = (torch.empty_like(sc) for _ in range(3))
+        gy = torch.randn_like(sc)
+        nblk = lib.xpt_res_join_bwd_blocks(M, N)
+        part = torch.empty(nblk * 3 * N, device=dev)
+        vec = (P(bn.weight), P(bn.bias), P(bn.running_mean), P(bn.running_var))
+
+        def fused():
+            xl.check(lib.xpt_res_join_fwd(P(x), K, P(w3h), P(b3), None, 0, None, None, 0, P(sc), *vec, rn2.RES_BN_EPS, P(out), P(pre),
+                                          M, K, N, 1, h, w, h, w, torch.cuda.current_stream().cuda_stream), "fwd")
+
+        def composed():
+            with torch.no_grad():
+                ops.res_join_torch(x, w3h.view(N, K, 1, 1), b3, bn, rn2.RES_BN_EPS, shortcut=sc)
+
+        def bwd():
+            xl.check(lib.xpt_res_join_bwd(P(gy), P(gy), P(out), *vec, rn2.RES_BN_EPS, P(g), None, P(part), part.numel(), M, N, 1,
+                                          h, w, h, w, torch.cuda.current_stream().cuda_stream), "bwd")
+
+        rows.append({"K": K, "N": N, "rows": M, "fused_fwd_us": round(graph_time(fused), 2),
+                     "composed_fwd_us": round(graph_time(composed), 2), "bwd_us": round(graph_time(bwd), 2), "bwd_blocks": nblk})
+        scale *= stride1
+    return {"widths": rows, "how": f"{repeats} calls back to back in a captured graph, {rounds} replays between HIP events; hot caches"}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("backbone", nargs="?", default="MobileNetV2")
@@ -129,6 +192,8 @@ def main():
               "captured": graph is not None and graph.graph is not None, "first_loss": first, "final_loss": float(out[1])}
     if os.environ.get("XPT_BENCH_DW") == "1" and args.backbone == "MobileNetV2":
         result["depthwise_stage"] = depthwise_stage_floor(torch.device("cuda:0"), args.batch, args.height, args.width)
+    if os.environ.get("XPT_BENCH_JUNCTION") == "1" and args.backbone == "ResNet50V2":
+        result["junction"] = junction_hot_replay(torch.device("cuda:0"), args.batch, args.height, args.width)
     print(json.dumps(result))
 
 

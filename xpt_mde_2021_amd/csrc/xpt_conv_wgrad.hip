@@ -449,7 +449,7 @@ bool plan_for(int wn, int wc, int B, int C, int N, int KH, int KW, int stride, i
   p.WN = wn; p.WC = wc;
   p.WT = 4 / (wn * wc);
   const int taps = (T + p.WT - 1) / p.WT;
-  const int allowed[] = {1, 3, 5, 7, 9};
+  const int allowed[] = {1, 3, 5, 7, 9, 13};               // (13: a quarter of a 7 x 7 filter, the ResNet50V2 stem)
   p.TAPS = 0;
   for (int v : allowed)
     if (v >= taps) { p.TAPS = v; break; }
@@ -592,6 +592,7 @@ extern "C" int xpt_conv2d_bwd_weight_partials(const void* g, const void* x, floa
     XPT_WGRAD_CASE(5)
     XPT_WGRAD_CASE(7)
     XPT_WGRAD_CASE(9)
+    XPT_WGRAD_CASE(13)
     default:
       return XPT_ERR_ARG;
   }

@@ -178,7 +178,7 @@ class _Conv2dSame(torch.autograd.Function):
     """y = LeakyReLU_slope(conv2d_same(x [nearest-2x up-sampled], weight, stride) + bias)."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, stride, slope, upsample, valid):
+    def forward(ctx, x, weight, bias, stride, slope, upsample, valid, pad):
         lib = _lib.load()
         global _tuned
         if not _tuned:
@@ -192,7 +192,15 @@ class _Conv2dSame(torch.autograd.Function):
         if Cx != Cp:
             raise _lib.XptHipError(f"conv: input has {Cx} channels, the packed weight expects {Cp} (= {C} padded to 8)")
         H, W = PH << upsample, PW << upsample
-        if valid:                                   # keras padding="valid" (the NASNet stem)
+        if pad >= 0:                                # ZeroPadding2D(pad) + padding="valid" (keras resnet_v2: conv1_pad, <name>_2_pad)
+            if valid or 2 * pad > KH - 1 or 2 * pad > KW - 1:
+                raise _lib.XptHipError(f"conv: explicit padding {pad} with a {KH} x {KW} filter (valid={valid})")
+            pt = pl = pad
+            OH, OW = (H + 2 * pad - KH) // stride + 1, (W + 2 * pad - KW) // stride + 1
+            # at stride 1 symmetric (k - 1) / 2 IS TF SAME: every specialised path below serves it; anything else takes the
+            # general implicit-GEMM kernel, which reads pad_t / pad_l and bounds-checks the far side
+            valid = not (stride == 1 and 2 * pad == KH - 1 and KH == KW)
+        elif valid:                                 # keras padding="valid" (the NASNet stem)
             pt = pl = 0
             OH, OW = (H - KH) // stride + 1, (W - KW) // stride + 1
         else:
@@ -306,7 +314,7 @@ class _Conv2dSame(torch.autograd.Function):
                                                    Cp, KH, KW, stride, pt, pl, PH, PW, Cp, ups, _stream()), "xpt_conv2d_bwd_data")
         if _deferred and getattr(weight, "flush_wgrads", False):
             _flush_deferred(True)
-        return dx, dw, dbias, None, None, None, None
+        return dx, dw, dbias, None, None, None, None, None
 
 
 # The decoder's weight gradients as ONE parallel branch of the step: a fork per layer costs more than it returns (below), so the
@@ -373,10 +381,13 @@ def _weight_grad(ctx, lib, g, gpitch, x):
     return ws[:nsplit * n].view(nsplit, N, KH, KW, C).sum(0).permute(0, 3, 1, 2)
 
 
-def conv2d_same(x, weight, bias, stride=1, slope=1.0, upsample=False, valid=False):
+def conv2d_same(x, weight, bias, stride=1, slope=1.0, upsample=False, valid=False, pad=None):
     """x [B,Cp,H,W] bf16 (NCHW-indexed, NHWC-stored; Cp = weight's input channels rounded up to 8, pad channels zero),
-    weight [N,C,KH,KW] float32 master, bias [N] float32 or None -> [B,N,ceil(2^u H / stride),ceil(2^u W / stride)] bf16."""
-    return _Conv2dSame.apply(x, weight, bias, int(stride), float(slope), bool(upsample), bool(valid))
+    weight [N,C,KH,KW] float32 master, bias [N] float32 or None -> [B,N,ceil(2^u H / stride),ceil(2^u W / stride)] bf16.
+    pad = p (an int, 2 p <= k - 1): `p` zeros on EVERY side and then a VALID convolution instead of TF SAME -- keras
+    ZeroPadding2D(p) + Conv2D(padding="valid"), output (H + 2 p - k) // stride + 1; forward, data and weight gradient read the
+    padding as out-of-range taps (no F.pad launch).  On an even extent at stride 2 this is NOT SAME, which pads (0, 1)."""
+    return _Conv2dSame.apply(x, weight, bias, int(stride), float(slope), bool(upsample), bool(valid), -1 if pad is None else int(pad))
 
 
 def usable(x, conv, slope):

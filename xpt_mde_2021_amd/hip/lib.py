@@ -223,6 +223,12 @@ SIGNATURES = {
     "xpt_se_scale_bwd_reduce": (_i, [_p, _p, ctypes.c_longlong, _p, _z, _p, _i, _i, _i, _i, _p]),
     "xpt_se_excite_bwd": (_i, [_p] * 11 + [_i, _i, _i, _p]),
     "xpt_dwconv_bn_swish_bwd": (_i, [_p, _p, _p, ctypes.c_longlong, _p, _p, _p, _p, _p, _p, _f, _p, _p, _z] + [_i] * 11 + [_p]),
+    "xpt_res_join_fwd": (_i, [_p, ctypes.c_longlong, _p, _p, _p, ctypes.c_longlong, _p, _p, _i, _p, _p, _p, _p, _p, _f, _p, _p,
+                              ctypes.c_longlong, _i, _i, _i, _i, _i, _i, _i, _p]),
+    "xpt_res_join_bwd_blocks": (_i, [ctypes.c_longlong, _i]),
+    "xpt_res_join_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _f, _p, _p, _p, _z, ctypes.c_longlong, _i, _i, _i, _i, _i, _i, _p]),
+    "xpt_maxpool3s2_zero_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "xpt_maxpool3s2_zero_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
 }
 
 

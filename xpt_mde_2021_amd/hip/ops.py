@@ -1131,6 +1131,224 @@ def mbconv_se_torch(h, dw_weight, dw_bn, se_reduce_w, se_reduce_b, se_expand_w, 
     return y * gate.view(B, C, 1, 1)
 
 
+# ------------------------------------------------------------------------------- ResNet50V2 junction and pool1
+def _half_weight(weight):
+    """[N, K] 16-bit operand of a 1x1 kernel: the shadow copy the fused Adam kernel keeps current when there is one."""
+    shadow = getattr(weight, "shadow_bf16", None)
+    w = shadow if shadow is not None else weight.detach().to(_lib.half())
+    return w.reshape(weight.shape[0], weight.shape[1]).contiguous()
+
+
+def _f32_vector(t, n, name):
+    t = t.detach()
+    if t.dtype != torch.float32 or not t.is_cuda or t.numel() != n or not t.is_contiguous():
+        raise _lib.XptHipError(f"res_join: {name} must be a contiguous float32 CUDA vector of {n} elements")
+    return t
+
+
+class _ResJoin(torch.autograd.Function):
+    """(out, pre) of one residual junction in one launch, its element-wise backward in one more (csrc/xpt_resnet.hip); the data
+    and weight gradients of the 1x1 convolutions are the existing GEMM kernels."""
+
+    @staticmethod
+    def forward(ctx, h, w3, b3, shortcut, sc_x, sc_w, sc_b, gamma, beta, mean, var, eps, stride):
+        lib = _lib.load()
+        if h.dtype != _lib.half() or not h.is_cuda:
+            raise _lib.XptHipError("res_join: expected 16-bit CUDA/HIP activations (no CPU fallback)")
+        B, K, OH, OW = h.shape
+        N = w3.shape[0]
+        h2 = as_rows(h)
+        M = h2.shape[0]
+        if h2.stride(0) % 8 or h2.data_ptr() % 16:
+            h2 = h2.contiguous()
+        w3h = _half_weight(w3)
+        b3_ = None if b3 is None else _f32_vector(b3, N, "b3")
+        g_, be_, mean, var = (_f32_vector(t, N, n) for t, n in ((gamma, "gamma"), (beta, "beta"), (mean, "mean"), (var, "var")))
+        IH = IW = 0
+        sc2 = scx2 = scwh = scb_ = None
+        if sc_x is not None:
+            if shortcut is not None or stride != 1 or tuple(sc_x.shape[2:]) != (OH, OW) or sc_x.shape[0] != B:
+                raise _lib.XptHipError("res_join: a conv shortcut is a stride-1 1x1 convolution of a map of the output's size")
+            scx2 = as_rows(sc_x.to(_lib.half()))
+            if scx2.stride(0) % 8 or scx2.data_ptr() % 16:
+                scx2 = scx2.contiguous()
+            scwh = _half_weight(sc_w)
+            scb_ = None if sc_b is None else _f32_vector(sc_b, N, "sc_b")
+        elif shortcut is not None:
+            IH, IW = shortcut.shape[2:]
+            want = (OH, OW) if stride == 1 else ((IH + 1) // 2, (IW + 1) // 2)
+            if shortcut.shape[0] != B or shortcut.shape[1] != N or want != (OH, OW):
+                raise _lib.XptHipError(f"res_join: shortcut {tuple(shortcut.shape)} does not fit the output {(B, N, OH, OW)} at "
+                                       f"stride {stride}")
+            sc2 = shortcut.to(_lib.half()).contiguous(memory_format=torch.channels_last)
+        elif stride != 1:
+            raise _lib.XptHipError("res_join: stride 2 needs a shortcut tensor")
+        out = torch.empty((B, N, OH, OW), dtype=_lib.half(), device=h.device, memory_format=torch.channels_last)
+        pre = torch.empty_like(out, memory_format=torch.channels_last)
+        _lib.check(lib.xpt_res_join_fwd(_ptr(h2), h2.stride(0) if M > 1 else K, _ptr(w3h), _ptr(b3_), _ptr(scx2),
+                                        0 if scx2 is None else (scx2.stride(0) if M > 1 else scx2.shape[1]), _ptr(scwh),
+                                        _ptr(scb_), 0 if scx2 is None else scx2.shape[1], _ptr(sc2), _ptr(g_), _ptr(be_),
+                                        _ptr(mean), _ptr(var), float(eps), _ptr(out), _ptr(pre), M, K, N, int(stride), OH, OW,
+                                        IH, IW, _stream()), "xpt_res_join_fwd")
+        ctx.save_for_backward(h2, w3h, scx2, scwh, out, g_, be_, mean, var)
+        ctx.cfg = (B, K, N, OH, OW, IH, IW, int(stride), float(eps), w3.shape, None if sc_w is None else sc_w.shape)
+        ctx.has = (b3 is not None, sc_b is not None)
+        vec = [p for p in (b3, sc_b, gamma, beta) if p is not None]
+        ctx.sink_vec = ((None if b3 is None else b3.flat_grad, None if sc_b is None else sc_b.flat_grad, gamma.flat_grad,
+                         beta.flat_grad) if all(grad_sink.wants(p) for p in vec) else None)
+        ctx.sink_w3 = w3.flat_grad if grad_sink.wants(w3) else None
+        ctx.sink_scw = sc_w.flat_grad if (sc_w is not None and grad_sink.wants(sc_w)) else None
+        ctx.set_materialize_grads(False)
+        return out, pre
+
+    @staticmethod
+    def _conv_grads(g2, x2, wh, sink_dst, wshape, need_dx, need_dw):
+        """(dx [M, K] or None, dW or None) of y = x2 wh^T given g2 = dL/dy."""
+        M, K = x2.shape
+        dx = dw = None
+        if need_dw and sink_dst is not None:
+            fused = need_dx and vector_rows(g2, g2.shape[1]) and vector_rows(x2, K)
+            dx = conv1x1_weight_grad_deferred(g2, x2, sink_dst, wh if fused else None)
+        elif need_dw:
+            dw = conv1x1_weight_grad(g2, x2).view(wshape)
+        if need_dx and dx is None:
+            dx = torch.mm(g2, wh)
+        return dx, dw
+
+    @staticmethod
+    def backward(ctx, g_out, g_pre):
+        lib = _lib.load()
+        h2, w3h, scx2, scwh, out, gamma, beta, mean, var = ctx.saved_tensors
+        B, K, N, OH, OW, IH, IW, stride, eps, w3shape, scwshape = ctx.cfg
+        if g_out is None and g_pre is None:
+            return (None,) * 13
+        M = B * OH * OW
+        dense = lambda t: None if t is None else t.to(_lib.half()).contiguous(memory_format=torch.channels_last)   # noqa: E731
+        g_out, g_pre = dense(g_out), dense(g_pre)
+        g = torch.empty((B, N, OH, OW), dtype=_lib.half(), device=out.device, memory_format=torch.channels_last)
+        gs = None
+        if stride == 2:
+            gs = torch.empty((B, N, IH, IW), dtype=_lib.half(), device=out.device, memory_format=torch.channels_last)
+        nblk = lib.xpt_res_join_bwd_blocks(M, N)
+        if nblk < 1:
+            raise _lib.XptHipError(f"xpt_res_join_bwd_blocks failed: {nblk}")
+        if ctx.sink_vec is not None:
+            ws = grad_sink.partials(ctx.sink_vec[3], "resjoin", nblk * 3 * N)
+        elif torch.cuda.is_current_stream_capturing():
+            # (torch.sum inside a captured step: a memset node this runtime replays wrongly, DESIGN.md section 6)
+            raise _lib.XptHipError("res_join backward without flat-gradient destinations inside a graph capture")
+        else:
+            ws = torch.empty(nblk * 3 * N, dtype=torch.float32, device=out.device)
+        _lib.check(lib.xpt_res_join_bwd(_ptr(g_out), _ptr(g_pre), _ptr(out), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(var), eps,
+                                        _ptr(g), _ptr(gs), _ptr(ws), ws.numel(), M, N, stride, OH, OW, IH, IW, _stream()),
+                   "xpt_res_join_bwd")
+        db3 = dscb = dgamma = dbeta = None
+        if ctx.sink_vec is not None:
+            dst_b3, dst_scb, dst_gamma, dst_beta = ctx.sink_vec
+            for dst, off in ((dst_b3, 0), (dst_scb, 0), (dst_beta, N), (dst_gamma, 2 * N)):
+                if dst is not None:
+                    grad_sink.add(dst, ws, off, N, nblk, 3 * N)
+        else:
+            tot = ws[:nblk * 3 * N].view(nblk, 3, N).sum(0)
+            db3 = tot[0].clone() if ctx.has[0] else None
+            dscb = tot[0].clone() if ctx.has[1] else None
+            dbeta, dgamma = tot[1], tot[2]
+        g2 = g.permute(0, 2, 3, 1).reshape(M, N)
+        need = ctx.needs_input_grad
+        dh, dw3 = _ResJoin._conv_grads(g2, h2, w3h, ctx.sink_w3, w3shape, need[0], need[1])
+        dscx = dscw = None
+        if scx2 is not None:
+            dscx, dscw = _ResJoin._conv_grads(g2, scx2, scwh, ctx.sink_scw, scwshape, need[4], need[5])
+            dscx = None if dscx is None else dscx.view(B, OH, OW, scx2.shape[1]).permute(0, 3, 1, 2)
+        dh = None if dh is None else dh.view(B, OH, OW, K).permute(0, 3, 1, 2)
+        dshort = None
+        if need[3]:
+            dshort = g if stride == 1 else gs
+        return dh, dw3, db3, dshort, dscx, dscw, dscb, dgamma, dbeta, None, None, None, None
+
+
+def res_join(h, w3, b3, bn, eps, shortcut=None, stride=1, sc_x=None, sc_w=None, sc_b=None):
+    """One residual junction of keras resnet_v2 `block2`: (out, pre) with
+        out = conv1x1(h, w3) + b3 + S,   pre = relu(bn(out))      (bn: the NEXT block's preact_bn, or post_bn; moving statistics)
+    S = shortcut (the block input; stride 2: its pixels (2 oy, 2 ox) = MaxPooling2D(1, strides=2)), or conv1x1(sc_x, sc_w) + sc_b
+    (`_0_conv` of the pre-activated input), or nothing.  16-bit CUDA activations run csrc/xpt_resnet.hip (one launch forward;
+    backward: one streaming launch + the pointwise data / weight-gradient kernels; parameter gradients through the GradSink
+    when the parameters live in flat buffers); host tensors and fp32 / fp64 inputs take res_join_torch."""
+    if stride not in (1, 2):
+        raise _lib.XptHipError("res_join: stride 1 or 2")
+    if h.is_cuda and h.dtype == _lib.half():
+        return _ResJoin.apply(h, w3, b3, shortcut, sc_x, sc_w, sc_b, bn.weight, bn.bias, bn.running_mean, bn.running_var,
+                              float(eps), int(stride))
+    return res_join_torch(h, w3, b3, bn, eps, shortcut, stride, sc_x, sc_w, sc_b)
+
+
+def res_join_torch(h, w3, b3, bn, eps, shortcut=None, stride=1, sc_x=None, sc_w=None, sc_b=None):
+    """The same junction as a GEMM plus element-wise framework ops, in h's dtype: the host / fp32 / fp64 path of res_join and the
+    yardstick its kernels are measured against (tests/test_resconv_gpu.py, tests/test_resnet50v2_gpu.py)."""
+    import torch.nn.functional as F
+    dt = h.dtype
+
+    def pointwise(x, w, b):
+        y = F.linear(x.permute(0, 2, 3, 1), w.flatten(1).to(dt), None if b is None else b.to(dt))
+        return y.permute(0, 3, 1, 2)
+
+    out = pointwise(h, w3, b3)
+    if sc_x is not None:
+        out = out + pointwise(sc_x.to(dt), sc_w, sc_b)
+    elif shortcut is not None:
+        out = out + (shortcut if stride == 1 else shortcut[:, :, ::2, ::2]).to(dt)
+    pre = F.relu(F.batch_norm(out, bn.running_mean.to(dt), bn.running_var.to(dt), bn.weight.to(dt), bn.bias.to(dt), False, 0.0,
+                              eps))
+    return out, pre
+
+
+class _MaxPool3s2Zero(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        lib = _lib.load()
+        x = _nhwc(x, "x")
+        if x.dtype != _lib.half():
+            raise _lib.XptHipError("maxpool3s2_zero: expected 16-bit activations")
+        B, C, H, W = x.shape
+        OH, OW = (H - 1) // 2 + 1, (W - 1) // 2 + 1
+        y = torch.empty((B, C, OH, OW), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
+        idx = torch.empty((B, OH, OW, C), dtype=torch.uint8, device=x.device)
+        _lib.check(lib.xpt_maxpool3s2_zero_fwd(_ptr(x), _ptr(y), _ptr(idx), B, H, W, C, OH, OW, _stream()),
+                   "xpt_maxpool3s2_zero_fwd")
+        ctx.save_for_backward(idx)
+        ctx.dims = (B, C, H, W, OH, OW)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        lib = _lib.load()
+        idx, = ctx.saved_tensors
+        B, C, H, W, OH, OW = ctx.dims
+        dy = dy.to(_lib.half()).contiguous(memory_format=torch.channels_last)
+        dx = torch.empty((B, C, H, W), dtype=_lib.half(), device=dy.device, memory_format=torch.channels_last)
+        _lib.check(lib.xpt_maxpool3s2_zero_bwd(_ptr(dy), _ptr(idx), _ptr(dx), B, H, W, C, OH, OW, _stream()),
+                   "xpt_maxpool3s2_zero_bwd")
+        return dx
+
+
+def maxpool3s2_zero(x):
+    """keras ZeroPadding2D(1) + MaxPooling2D(3, strides=2) (resnet_v2 pool1_pad / pool1_pool): the padding is 0.0 and takes part
+    in the max.  Tie rule: the FIRST maximal tap in row-major window order receives the gradient (a padded tap: nobody does)."""
+    if x.is_cuda and x.dtype == _lib.half():
+        return _MaxPool3s2Zero.apply(x)
+    return maxpool3s2_zero_torch(x)
+
+
+def maxpool3s2_zero_torch(x):
+    """The same pooling in framework ops, any dtype, with the tie rule spelled out: a one-hot of the first maximal tap."""
+    import torch.nn.functional as F
+    win = F.pad(x, (1, 1, 1, 1)).unfold(2, 3, 2).unfold(3, 3, 2)            # [B, C, OH, OW, 3, 3]: taps row-major
+    win = win.reshape(*win.shape[:4], 9)
+    eq = win == win.max(-1, keepdim=True).values
+    first = eq & (eq.cumsum(-1) == 1)
+    return (win * first.to(win.dtype)).sum(-1)
+
+
 # ------------------------------------------------------------------------------- per-channel conv epilogues
 def _rows_with_pitch(t):
     """NCHW-indexed tensor -> (tensor, row pitch in elements) readable as [B*H*W rows, C] with unit channel stride:

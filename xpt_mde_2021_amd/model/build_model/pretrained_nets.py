@@ -1463,11 +1463,14 @@ def load_keras_weights(encoder, weights):
 class PretrainedModel:
     """pretrained_nets.py:11-117 interface: PretrainedModel(net_name, use_pt_weight).encoder() builds the module
     whose forward is the reference's `.encode(input_image)`."""
-    # (MobileNetV2: build_model/mobilenet_v2.py; EfficientNetB0 / B3 / B5 / B7: build_model/efficientnet.py)
-    SUPPORTED = ("NASNetMobile", "MobileNetV2", "EfficientNetB0", "EfficientNetB3", "EfficientNetB5", "EfficientNetB7")
+    # (MobileNetV2: build_model/mobilenet_v2.py; EfficientNetB0 / B3 / B5 / B7: build_model/efficientnet.py; ResNet50V2:
+    #  build_model/resnet_v2.py)
+    SUPPORTED = ("NASNetMobile", "MobileNetV2", "EfficientNetB0", "EfficientNetB3", "EfficientNetB5", "EfficientNetB7",
+                 "ResNet50V2")
     WEIGHT_ENV = {"NASNetMobile": "XPT_NASNET_WEIGHTS", "MobileNetV2": "XPT_MOBILENETV2_WEIGHTS",
                   "EfficientNetB0": "XPT_EFFICIENTNETB0_WEIGHTS", "EfficientNetB3": "XPT_EFFICIENTNETB3_WEIGHTS",
-                  "EfficientNetB5": "XPT_EFFICIENTNETB5_WEIGHTS", "EfficientNetB7": "XPT_EFFICIENTNETB7_WEIGHTS"}
+                  "EfficientNetB5": "XPT_EFFICIENTNETB5_WEIGHTS", "EfficientNetB7": "XPT_EFFICIENTNETB7_WEIGHTS",
+                  "ResNet50V2": "XPT_RESNET50V2_WEIGHTS"}
 
     def __init__(self, net_name, use_pt_weight):
         if net_name not in self.SUPPORTED:
@@ -1497,6 +1500,12 @@ class PretrainedModel:
             net = eff.EfficientNetEncoder(self.net_name)
             if self.weight_file:
                 eff.load_keras_weights(net, self.weight_file)
+            return net
+        if self.net_name == "ResNet50V2":
+            from . import resnet_v2 as rn2             # (imports this module)
+            net = rn2.ResNet50V2Encoder()
+            if self.weight_file:
+                rn2.load_keras_weights(net, self.weight_file)
             return net
         net = NASNetMobileEncoder()
         if self.weight_file:
