@@ -330,3 +330,54 @@ def test_gradients_land_on_their_parameters_through_the_gradient_sink(gpu_device
     # and the op's dx is the C ABI's (same kernels): against the fp64 reference of the whole middle in the 16-bit bound is the
     # encoder-level test's business (tests/test_efficientnet_gpu.py); here only that it is finite and not zero
     assert bool(torch.isfinite(dx1).all()) and float(dx1.float().abs().max()) > 0
+
+
+def cotangent_layouts(dz):
+    """dz (dense channels_last, C channels) three ways with the same values: as it is; channels [8, 8 + C) of a channels_last
+    tensor with C + 16 channels (16-byte aligned rows: read in place); channels [4, 4 + C) of such a tensor (base 8 bytes off a
+    16-byte boundary: copied first)."""
+    B, C, H, W = dz.shape
+    out = [dz]
+    for first in (8, 4):
+        wide = torch.full((B, C + 16, H, W), float("nan"), dtype=dz.dtype, device=dz.device).contiguous(memory_format=torch.channels_last)
+        wide[:, first:first + C] = dz
+        out.append(wide[:, first:first + C])
+        assert out[-1].stride() == (H * W * (C + 16), 1, W * (C + 16), C + 16) and torch.equal(out[-1], dz)
+        assert out[-1].data_ptr() % 16 == (0 if first == 8 else 8)
+    return out
+
+
+@pytest.mark.parametrize("shape", [(2, 5, 7, 16, 3, 1), (1, 6, 10, 24, 5, 2)], ids=lambda s: "x".join(str(v) for v in s))
+def test_backward_is_bit_identical_for_dense_in_place_and_copied_cotangent_slices(gpu_device, shape):
+    """hip.ops.mbconv_se backward with the cotangent dense, as an aligned channel slice (the 16-byte loads take it in place) and
+    as a misaligned one (copied): dx, the weight / gamma / beta gradients and the four squeeze-excite gradients are the same bits
+    all three times."""
+    from xpt_mde_2021_amd.hip import lib as xl, ops
+    from xpt_mde_2021_amd.model.build_model.pretrained_nets import FrozenBatchNorm
+    fmt = xl.half_format()
+    dtype, _ = FORMATS[fmt]
+    B, H, W, C, k, stride = shape
+    S = C // 4
+    c = case(shape, True, fmt)
+    e = excite_case(B, C, S)
+    dev = gpu_device
+    bn = FrozenBatchNorm(C).to(dev)
+    with torch.no_grad():
+        bn.weight.copy_(c["gamma"]), bn.bias.copy_(c["beta"]), bn.running_mean.copy_(c["mean"]), bn.running_var.copy_(c["var"])
+    P = lambda t: torch.nn.Parameter(t.float().to(dev))                                # noqa: E731
+    weight, wr, br, we, be = P(c["w"]), P(e["wr"].view(S, C, 1, 1)), P(e["br"]), P(e["we"].view(C, S, 1, 1)), P(e["be"])
+    params = (weight, bn.weight, bn.bias, wr, br, we, be)
+    x = c["x"].to(dtype).to(dev).contiguous(memory_format=torch.channels_last)
+    dz = c["dz"].to(dtype).to(dev).contiguous(memory_format=torch.channels_last)
+    results = []
+    for cot in cotangent_layouts(dz):
+        for p in params:
+            p.grad = None
+        xin = x.clone().requires_grad_(True)
+        ops.mbconv_se(xin, weight, bn, wr, br, we, be, k, stride, act_in=True, eps=EPS).backward(cot)
+        results.append([xin.grad] + [p.grad.clone() for p in params])
+    torch.cuda.synchronize()
+    assert all(bool(torch.isfinite(g).all()) and float(g.float().abs().max()) > 0 for g in results[0])
+    for name, dense, in_place, copied in zip(("dx", "dw", "dgamma", "dbeta", "dW_r", "db_r", "dW_e", "db_e"), *results):
+        assert torch.equal(dense, in_place), f"{name}: in-place slice"
+        assert torch.equal(dense, copied), f"{name}: copied slice"

@@ -262,3 +262,49 @@ def test_autograd_op_equals_the_c_abi_and_the_torch_fallback_path(gpu_device):
     x32 = c["x"].float().to(gpu_device).requires_grad_(True)
     y32 = ops.dwconv_bn_relu6(x32, weight, bn, stride, act_in=True, eps=EPS)
     assert y32.dtype == torch.float32 and float((y32.double().cpu() - ref["y"]).abs().max()) <= 1e-4 * 6.0
+
+
+def cotangent_layouts(dy):
+    """dy (dense channels_last, C channels) three ways with the same values: as it is; channels [8, 8 + C) of a channels_last
+    tensor with C + 16 channels (16-byte aligned rows: read in place); channels [4, 4 + C) of such a tensor (base 8 bytes off a
+    16-byte boundary: copied first)."""
+    B, C, H, W = dy.shape
+    out = [dy]
+    for first in (8, 4):
+        wide = torch.full((B, C + 16, H, W), float("nan"), dtype=dy.dtype, device=dy.device).contiguous(memory_format=torch.channels_last)
+        wide[:, first:first + C] = dy
+        out.append(wide[:, first:first + C])
+        assert out[-1].stride() == (H * W * (C + 16), 1, W * (C + 16), C + 16) and torch.equal(out[-1], dy)
+        assert out[-1].data_ptr() % 16 == (0 if first == 8 else 8)
+    return out
+
+
+@pytest.mark.parametrize("shape", [(2, 5, 7, 16, 1), (1, 6, 10, 24, 2)], ids=lambda s: "x".join(str(v) for v in s))
+def test_backward_is_bit_identical_for_dense_in_place_and_copied_cotangent_slices(gpu_device, shape):
+    """hip.ops.dwconv_bn_relu6 backward with the cotangent dense, as an aligned channel slice (the 16-byte loads take it in place)
+    and as a misaligned one (copied): dx and the weight / gamma / beta gradients are the same bits all three times."""
+    from xpt_mde_2021_amd.hip import lib as xl, ops
+    from xpt_mde_2021_amd.model.build_model.pretrained_nets import FrozenBatchNorm
+    fmt = xl.half_format()
+    dtype, _ = FORMATS[fmt]
+    B, H, W, C, stride = shape
+    c = case(shape, True, fmt)
+    bn = FrozenBatchNorm(C).to(gpu_device)
+    with torch.no_grad():
+        bn.weight.copy_(c["gamma"]), bn.bias.copy_(c["beta"]), bn.running_mean.copy_(c["mean"]), bn.running_var.copy_(c["var"])
+    weight = torch.nn.Parameter(c["w"].float().to(gpu_device))
+    params = (weight, bn.weight, bn.bias)
+    x = c["x"].to(dtype).to(gpu_device).contiguous(memory_format=torch.channels_last)
+    dy = c["dy"].to(dtype).to(gpu_device).contiguous(memory_format=torch.channels_last)
+    results = []
+    for cot in cotangent_layouts(dy):
+        for p in params:
+            p.grad = None
+        xin = x.clone().requires_grad_(True)
+        ops.dwconv_bn_relu6(xin, weight, bn, stride, act_in=True, eps=EPS).backward(cot)
+        results.append([xin.grad] + [p.grad.clone() for p in params])
+    torch.cuda.synchronize()
+    assert all(bool(torch.isfinite(g).all()) and float(g.float().abs().max()) > 0 for g in results[0])
+    for name, dense, in_place, copied in zip(("dx", "dw", "dgamma", "dbeta"), *results):
+        assert torch.equal(dense, in_place), f"{name}: in-place slice"
+        assert torch.equal(dense, copied), f"{name}: copied slice"

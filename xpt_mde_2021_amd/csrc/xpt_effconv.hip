@@ -4,8 +4,7 @@
 // (include_top=False; config-example.py JOINT_NET "depth", RIGID_EF0 / EF3 / EF5 / EF7); the `block` function of keras
 // efficientnet.py is expand 1x1 -> BN -> swish -> DepthwiseConv2D k x k -> BN -> swish -> GlobalAveragePooling2D -> Conv2D 1x1
 // (bias, swish) -> Conv2D 1x1 (bias, sigmoid) -> multiply -> project 1x1 -> BN (+ input).  The two pointwise halves are
-// xpt_pwconv_bn_fwd / xpt_conv1x1_bn_bwd_fused; this file is everything between them.  xpt_mbconv.hip (MobileNetV2) knows 3x3
-// windows and ReLU6 only, and nothing there pools or gates.
+// xpt_pwconv_bn_fwd / xpt_conv1x1_bn_bwd_fused; this file is everything between them.
 //
 //   sw(v)  = v sigma(v),   sw'(v) = sigma(v) (1 + v (1 - sigma(v)))
 //   a(v)   = sw(v) when act_in (the swish behind the PRECEDING BatchNorm, whose producer stores its pre-activation output), else v
@@ -14,69 +13,25 @@
 //   p[b,c] = mean_hw sw(v),   r = W_r p + b_r,   q = sw(r),   e = W_e q + b_e,   gate = sigma(e)
 //   z      = sw(v) gate[b,c]                                                                     (input of the projection)
 //
-// Activations NHWC in the 16-bit format of the build, parameters and accumulation fp32.  A lane owns 8 channels (16 bytes) of a
-// pixel; activation loads are 16-byte buffer loads whose range check supplies the zeros of the halo (xpt_mbconv.hip).  Every
-// kernel that sums over pixels (the pool of the forward, dL/dgate, the parameter gradients of the depthwise stage) uses ONE
-// plan: a workgroup owns a chunk of output rows of ONE image and a block of channel groups, its lanes walk the chunk's pixels,
-// the workgroup adds them through LDS in lane order and writes one row of a partial matrix; rows are added in row order by
-// whoever finishes them.  No atomics, so a captured step replays bit for bit.  The k x k weights of the workgroup's channel
-// block sit in LDS ([tap][channel]: 25 x 8 weights per lane do not fit the register file next to 25 x 8 accumulators).
+// Activations NHWC in the 16-bit format of the build, parameters and accumulation fp32; the 16-byte loads, the halo and the ONE
+// row-chunk plan of every kernel that sums over pixels (the pool of the forward, dL/dgate, the parameter gradients of the
+// depthwise stage) are those of xpt_dwstage.h.  The k x k weights of the workgroup's channel block sit in LDS ([tap][channel]:
+// 25 x 8 weights per lane do not fit the register file next to 25 x 8 accumulators).
 //
-// The depthwise kernels gather through L2 as the MobileNetV2 stage does: no LDS tile of the input yet.
-#include "xpt_common.h"
+// The depthwise kernels gather through L2: no LDS tile of the input yet.
+#include "xpt_dwstage.h"
 
 namespace {
 
-typedef unsigned int ef_u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr unsigned EF_OOB = 0x80000000u;        // byte offset no buffer of < 2^31 bytes contains: the load returns zeros
 constexpr int EF_MAX_CGB = 32;                  // channel groups per workgroup at most (LDS: k k x 256 weights)
-constexpr int EF_PASS = 4;                      // entries per LDS pass of the backward's workgroup sum
 constexpr int EF_LDS_FLOATS = 12288;            // dynamic LDS of the excite kernels (48 KiB)
 constexpr int EF_CB = 64;                       // channels per workgroup of the excite backward
-
-struct EfDims {
-  int B, H, W, C, OH, OW, pad_t, pad_l;
-};
-
-struct EfPlan {
-  int rpc;       // output rows per chunk
-  int cpi;       // chunks per image
-  int chunks;    // B * cpi: rows of a partial matrix
-  int cgb;       // channel groups per workgroup (a divisor of C / 8, <= EF_MAX_CGB)
-  int ncb;       // channel blocks: (C / 8) / cgb
-};
 
 __device__ __forceinline__ float ef_sigmoid(float v) { return 1.0f / (1.0f + __expf(-v)); }
 __device__ __forceinline__ float ef_swish(float v) { return v * ef_sigmoid(v); }
 __device__ __forceinline__ float ef_dswish(float v) {
   const float g = ef_sigmoid(v);
   return g * (1.0f + v * (1.0f - g));
-}
-
-__device__ __forceinline__ void ef_unpack(const ef_u32x4& v, float (&f)[8]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f[2 * i] = xpt_h2f_lo(v[i]);
-    f[2 * i + 1] = xpt_h2f_hi(v[i]);
-  }
-}
-
-__device__ __forceinline__ uint4 ef_pack(const float (&f)[8]) {
-  unsigned p[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) p[i] = (unsigned)xpt_f2h(f[2 * i]) | ((unsigned)xpt_f2h(f[2 * i + 1]) << 16);
-  return make_uint4(p[0], p[1], p[2], p[3]);
-}
-
-__device__ __forceinline__ ef_u32x4 ef_load16(const void* p, size_t element) {
-  const uint4 v = *(const uint4*)((const unsigned short*)p + element);
-  return ef_u32x4{v.x, v.y, v.z, v.w};
-}
-
-__device__ __forceinline__ void ef_load8f(const float* p, float (&f)[8]) {
-  const float4 a = ((const float4*)p)[0], b = ((const float4*)p)[1];
-  f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = b.x; f[5] = b.y; f[6] = b.z; f[7] = b.w;
 }
 
 // the workgroup of a unit: chunk (= image b, row chunk oyc) and channel block cb; the lane: (pixel lane pl, channel group cgl)
@@ -86,7 +41,7 @@ struct EfWho {
   bool active;
 };
 
-__device__ __forceinline__ EfWho ef_who(unsigned unit, const EfPlan& p, int OH) {
+__device__ __forceinline__ EfWho ef_who(unsigned unit, const DwPlan& p, int OH) {
   EfWho w;
   w.chunk = xpt_divmod(unit, (unsigned)p.ncb, w.cb);
   unsigned oyc;
@@ -130,7 +85,7 @@ template <int K, int S, int ACT>
 __global__ __launch_bounds__(256) void ef_dw_fwd_kernel(const void* __restrict__ x, const float* __restrict__ w,
                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
                                                          const float* __restrict__ mean, const float* __restrict__ var, float eps,
-                                                         void* __restrict__ vout, float* __restrict__ pool, EfDims d, EfPlan p,
+                                                         void* __restrict__ vout, float* __restrict__ pool, DwDims d, DwPlan p,
                                                          unsigned xbytes, unsigned nunits, int xcd_on) {
   constexpr int KK = K * K;
   __shared__ float wl[KK][256];
@@ -166,18 +121,18 @@ __global__ __launch_bounds__(256) void ef_dw_fwd_kernel(const void* __restrict__
       for (int ky = 0; ky < K; ++ky) {
         const int iy = iy0 + ky;
         const bool rowok = (unsigned)iy < (unsigned)d.H;
-        ef_u32x4 t[K];
+        dw_u32x4 t[K];
 #pragma unroll
         for (int kx = 0; kx < K; ++kx) {
           const int ix = ix0 + kx;
           const bool ok = rowok && (unsigned)ix < (unsigned)d.W;
-          t[kx] = __builtin_amdgcn_raw_buffer_load_b128(rx, ok ? base + (unsigned)iy * rowpitch + (unsigned)ix * pix : EF_OOB, 0, 0);
+          t[kx] = __builtin_amdgcn_raw_buffer_load_b128(rx, ok ? base + (unsigned)iy * rowpitch + (unsigned)ix * pix : DW_OOB, 0, 0);
         }
 #pragma unroll
         for (int kx = 0; kx < K; ++kx) {
           float a[8], wk[8];
-          ef_unpack(t[kx], a);
-          ef_load8f(&wl[ky * K + kx][who.cgl * 8u], wk);
+          dw_unpack(t[kx], a);
+          dw_load8f(&wl[ky * K + kx][who.cgl * 8u], wk);
 #pragma unroll
           for (int j = 0; j < 8; ++j) acc[j] += wk[j] * (ACT ? ef_swish(a[j]) : a[j]);       // (sw(0) = 0: the halo stays zero)
         }
@@ -189,7 +144,7 @@ __global__ __launch_bounds__(256) void ef_dw_fwd_kernel(const void* __restrict__
         ps[j] += ef_swish(r[j]);                                                             // the fp32 value, before the store rounds it
       }
       const size_t e = ((size_t)(who.b * (unsigned)d.OH + oy) * (unsigned)d.OW + ox) * (unsigned)d.C + who.cg * 8u;
-      *(uint4*)((unsigned short*)vout + e) = ef_pack(r);
+      *(uint4*)((unsigned short*)vout + e) = dw_pack(r);
     }
   }
   ef_column_sums(ps, who, red, pool + (size_t)who.chunk * (unsigned)d.C);
@@ -309,16 +264,16 @@ __global__ __launch_bounds__(256) void ef_scale_fwd_kernel(const void* __restric
   const unsigned pixel = xpt_divmod(item, CG, cg);
   const unsigned b = xpt_divmod(pixel, HW, hw);
   float f[8], g[8];
-  ef_unpack(ef_load16(v, (size_t)item * 8u), f);
-  ef_load8f(gate + ((size_t)b * CG + cg) * 8u, g);
+  dw_unpack(dw_load16(v, (size_t)item * 8u), f);
+  dw_load8f(gate + ((size_t)b * CG + cg) * 8u, g);
 #pragma unroll
   for (int j = 0; j < 8; ++j) f[j] = ef_swish(f[j]) * g[j];
-  *(uint4*)((unsigned short*)z + (size_t)item * 8u) = ef_pack(f);
+  *(uint4*)((unsigned short*)z + (size_t)item * 8u) = dw_pack(f);
 }
 
 // partial rows of dL/dgate[b,c] = sum_hw dz sw(v)
 __global__ __launch_bounds__(256) void ef_dgate_kernel(const void* __restrict__ v, const void* __restrict__ dz, unsigned dz_pitch,
-                                                        float* __restrict__ part, int OH, int OW, int C, EfPlan p,
+                                                        float* __restrict__ part, int OH, int OW, int C, DwPlan p,
                                                         unsigned nunits, int xcd_on) {
   __shared__ float red[8][256];
   unsigned unit;
@@ -332,8 +287,8 @@ __global__ __launch_bounds__(256) void ef_dgate_kernel(const void* __restrict__ 
     const size_t first = ((size_t)who.b * (unsigned)OH + (unsigned)who.oy0) * (unsigned)OW;
     for (unsigned i = who.pl; i < nout; i += who.PXT) {
       float f[8], g[8];
-      ef_unpack(ef_load16(v, (first + i) * (unsigned)C + who.cg * 8u), f);
-      ef_unpack(ef_load16(dz, (first + i) * dz_pitch + who.cg * 8u), g);
+      dw_unpack(dw_load16(v, (first + i) * (unsigned)C + who.cg * 8u), f);
+      dw_unpack(dw_load16(dz, (first + i) * dz_pitch + who.cg * 8u), g);
 #pragma unroll
       for (int j = 0; j < 8; ++j) ps[j] += g[j] * ef_swish(f[j]);
     }
@@ -354,12 +309,7 @@ __global__ __launch_bounds__(256) void ef_finish_rows_kernel(const float* __rest
 }
 
 // ------------------------------------------------------------------------------------------------ depthwise backward
-// first input row of the chunk that starts at output row oy: the chunks of an image tile its input rows [0, H)
-__device__ __forceinline__ int ef_in_row(int oy, int S, int OH, int H) {
-  return oy <= 0 ? 0 : (oy >= OH ? H : min(H, oy * S));
-}
-
-// re-indexed over the INPUT pixel (xpt_mbconv.hip): the lane of input pixel q gathers gz = sw'(v) (dz gate + dp / (OH OW)) at
+// re-indexed over the INPUT pixel: the lane of input pixel q gathers gz = sw'(v) (dz gate + dp / (OH OW)) at
 // the (up to k k) outputs that read q
 template <int K, int S, int ACT>
 __global__ __launch_bounds__(256) void ef_dw_bwd_kernel(const void* __restrict__ x, const void* __restrict__ v,
@@ -367,17 +317,17 @@ __global__ __launch_bounds__(256) void ef_dw_bwd_kernel(const void* __restrict__
                                                          const float* __restrict__ gate, const float* __restrict__ dp, float inv_hw,
                                                          const float* __restrict__ w, const float* __restrict__ gamma,
                                                          const float* __restrict__ mean, const float* __restrict__ var, float eps,
-                                                         void* __restrict__ dx, float* __restrict__ partials, EfDims d, EfPlan p,
+                                                         void* __restrict__ dx, float* __restrict__ partials, DwDims d, DwPlan p,
                                                          unsigned vbytes, unsigned dzbytes, unsigned nunits, int xcd_on) {
   constexpr int KK = K * K, NE = KK + 2;
   __shared__ float wl[KK][256];
-  __shared__ float red[EF_PASS * 8][256];
+  __shared__ float red[DW_PASS * 8][256];
   unsigned unit;
   if (!xpt_xcd_unit(xcd_on != 0, blockIdx.x, nunits, unit)) return;          // (uniform over the workgroup)
   const EfWho who = ef_who(unit, p, d.OH);
   ef_stage_weights<KK>(w, who, wl);
   __syncthreads();
-  const int r0 = ef_in_row(who.oy0, S, d.OH, d.H), r1 = ef_in_row(who.oy1, S, d.OH, d.H);
+  const int r0 = dw_in_row(who.oy0, S, d.OH, d.H), r1 = dw_in_row(who.oy1, S, d.OH, d.H);
   const unsigned npix = (unsigned)(r1 - r0) * (unsigned)d.W;
   const unsigned cg = who.cg, b = who.b;
 
@@ -391,8 +341,8 @@ __global__ __launch_bounds__(256) void ef_dw_bwd_kernel(const void* __restrict__
   }
   if (who.active) {
     float gt[8], dpn[8];
-    ef_load8f(gate + (size_t)b * (unsigned)d.C + cg * 8u, gt);
-    ef_load8f(dp + (size_t)b * (unsigned)d.C + cg * 8u, dpn);
+    dw_load8f(gate + (size_t)b * (unsigned)d.C + cg * 8u, gt);
+    dw_load8f(dp + (size_t)b * (unsigned)d.C + cg * 8u, dpn);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       const unsigned c = cg * 8 + j;
@@ -409,7 +359,7 @@ __global__ __launch_bounds__(256) void ef_dw_bwd_kernel(const void* __restrict__
       const int iy = r0 + (int)xpt_divmod(i, (unsigned)d.W, ix);
       const size_t xe = ((size_t)(b * (unsigned)d.H + (unsigned)iy) * (unsigned)d.W + ix) * (unsigned)d.C + cg * 8u;
       float xa[8], slope[8], ds[8];
-      ef_unpack(ef_load16(x, xe), xa);
+      dw_unpack(dw_load16(x, xe), xa);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         slope[j] = ACT ? ef_dswish(xa[j]) : 1.f;
@@ -422,7 +372,7 @@ __global__ __launch_bounds__(256) void ef_dw_bwd_kernel(const void* __restrict__
         const int ty = iy + d.pad_t - ky;
         const int oy = S == 2 ? ty >> 1 : ty;
         const bool yok = ty >= 0 && (S == 1 || (ty & 1) == 0) && oy < d.OH;
-        ef_u32x4 tv[K], td[K];
+        dw_u32x4 tv[K], td[K];
         bool oks[K];
 #pragma unroll
         for (int kx = 0; kx < K; ++kx) {
@@ -431,17 +381,17 @@ __global__ __launch_bounds__(256) void ef_dw_bwd_kernel(const void* __restrict__
           const bool ok = yok && tx >= 0 && (S == 1 || (tx & 1) == 0) && ox < d.OW;
           const unsigned opix = (b * (unsigned)d.OH + (unsigned)oy) * (unsigned)d.OW + (unsigned)ox;
           oks[kx] = ok;
-          tv[kx] = __builtin_amdgcn_raw_buffer_load_b128(rv, ok ? opix * pix + cg * 16u : EF_OOB, 0, 0);
-          td[kx] = __builtin_amdgcn_raw_buffer_load_b128(rd, ok ? opix * dz_pitch_bytes + cg * 16u : EF_OOB, 0, 0);
+          tv[kx] = __builtin_amdgcn_raw_buffer_load_b128(rv, ok ? opix * pix + cg * 16u : DW_OOB, 0, 0);
+          td[kx] = __builtin_amdgcn_raw_buffer_load_b128(rd, ok ? opix * dz_pitch_bytes + cg * 16u : DW_OOB, 0, 0);
         }
 #pragma unroll
         for (int kx = 0; kx < K; ++kx) {
           constexpr int centre = (K / 2) * K + K / 2;
           const int k = ky * K + kx;
           float vv[8], gz[8], wk[8];
-          ef_unpack(tv[kx], vv);
-          ef_unpack(td[kx], gz);
-          ef_load8f(&wl[k][who.cgl * 8u], wk);
+          dw_unpack(tv[kx], vv);
+          dw_unpack(td[kx], gz);
+          dw_load8f(&wl[k][who.cgl * 8u], wk);
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
             gz[j] = oks[kx] ? ef_dswish(vv[j]) * (gz[j] * gt[j] + dpn[j]) : 0.f;      // (no output there: sw'(0) dp / HW is not zero)
@@ -455,7 +405,7 @@ __global__ __launch_bounds__(256) void ef_dw_bwd_kernel(const void* __restrict__
         float r[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) r[j] = slope[j] * sc[j] * ds[j];
-        *(uint4*)((unsigned short*)dx + xe) = ef_pack(r);
+        *(uint4*)((unsigned short*)dx + xe) = dw_pack(r);
       }
     }
   }
@@ -468,7 +418,7 @@ __global__ __launch_bounds__(256) void ef_dw_bwd_kernel(const void* __restrict__
 #pragma unroll
   for (int k = 0; k < KK; ++k) {
     float wk[8];
-    ef_load8f(&wl[k][who.cgl * 8u], wk);
+    dw_load8f(&wl[k][who.cgl * 8u], wk);
 #pragma unroll
     for (int j = 0; j < 8; ++j) dot[j] += wk[j] * G[k][j];
   }
@@ -476,12 +426,12 @@ __global__ __launch_bounds__(256) void ef_dw_bwd_kernel(const void* __restrict__
   float* prow = partials + (size_t)who.chunk * NE * (unsigned)d.C;
   const unsigned CGB = who.CGB;
 #pragma unroll
-  for (int pass = 0; pass < (NE + EF_PASS - 1) / EF_PASS; ++pass) {
+  for (int pass = 0; pass < (NE + DW_PASS - 1) / DW_PASS; ++pass) {
     __syncthreads();                                                     // the previous pass has been read
     if (who.active) {
 #pragma unroll
-      for (int el = 0; el < EF_PASS; ++el) {
-        const int e = pass * EF_PASS + el;
+      for (int el = 0; el < DW_PASS; ++el) {
+        const int e = pass * DW_PASS + el;
         if (e < NE) {
 #pragma unroll
           for (int j = 0; j < 8; ++j)
@@ -490,14 +440,14 @@ __global__ __launch_bounds__(256) void ef_dw_bwd_kernel(const void* __restrict__
       }
     }
     __syncthreads();
-    const int ne = min(EF_PASS, NE - pass * EF_PASS);
+    const int ne = min(DW_PASS, NE - pass * DW_PASS);
     const unsigned nout = (unsigned)ne * 8u * CGB;
     for (unsigned o = threadIdx.x; o < nout; o += 256u) {
       unsigned gl;
       const unsigned q = xpt_divmod(o, CGB, gl);                         // q = el * 8 + j
       float sum = 0.f;
       for (unsigned t = 0; t < who.PXT; ++t) sum += red[q][t * CGB + gl];
-      const unsigned e = (unsigned)pass * EF_PASS + (q >> 3), c = (who.cb * CGB + gl) * 8u + (q & 7u);
+      const unsigned e = (unsigned)pass * DW_PASS + (q >> 3), c = (who.cb * CGB + gl) * 8u + (q & 7u);
       const unsigned at = e < (unsigned)KK ? c * KK + e : (e * (unsigned)d.C + c);   // KK C + c (gamma), (KK + 1) C + c (beta)
       prow[at] = sum;
     }
@@ -505,51 +455,11 @@ __global__ __launch_bounds__(256) void ef_dw_bwd_kernel(const void* __restrict__
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-bool ef_aligned(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
 int ef_check_map(int B, int OH, int OW, int C) {
   if (B <= 0 || OH <= 0 || OW <= 0 || C <= 0) return XPT_ERR_SHAPE;
   if (C % 8 != 0) return XPT_ERR_ARG;                                    // 16-byte channel groups
   if ((long long)B * OH * OW * C * 2 >= (1LL << 31)) return XPT_ERR_SHAPE;
   return XPT_OK;
-}
-
-int ef_check(const EfDims& d, int k, int stride) {
-  if (d.B <= 0 || d.H <= 0 || d.W <= 0 || d.C <= 0 || d.OH <= 0 || d.OW <= 0) return XPT_ERR_SHAPE;
-  if (d.C % 8 != 0) return XPT_ERR_ARG;
-  if (k != 3 && k != 5) return XPT_ERR_ARG;
-  if (stride != 1 && stride != 2) return XPT_ERR_ARG;
-  if (d.pad_t < 0 || d.pad_t > k / 2 || d.pad_l < 0 || d.pad_l > k / 2) return XPT_ERR_ARG;
-  // the centre of every window inside the input (SAME padding of an odd window, either stride, any parity)
-  if ((long long)(d.OH - 1) * stride + k / 2 - d.pad_t > d.H - 1 || (long long)(d.OW - 1) * stride + k / 2 - d.pad_l > d.W - 1)
-    return XPT_ERR_SHAPE;
-  // 32-bit byte offsets below the out-of-range marker
-  if ((long long)d.B * d.H * d.W * d.C * 2 >= (1LL << 31) || (long long)d.B * d.OH * d.OW * d.C * 2 >= (1LL << 31))
-    return XPT_ERR_SHAPE;
-  return XPT_OK;
-}
-
-EfPlan ef_plan(int B, int OH, int OW, int C) {
-  EfPlan p;
-  const int CG = C / 8;
-  int cgb = 1;
-  for (int dv = 1; dv <= EF_MAX_CGB && dv <= CG; ++dv)
-    if (CG % dv == 0) cgb = dv;
-  auto groups = [&](int rpc, int g) { return (long long)B * ((OH + rpc - 1) / rpc) * (CG / g); };
-  int rpc = 1;
-  while (rpc < OH && groups(rpc, cgb) > 2048) rpc *= 2;
-  // few workgroups (the 1/16 and 1/32 maps): spread over channel groups, down to one lane row per output pixel of the chunk
-  while (cgb > 1 && groups(rpc, cgb) < 512 && 256 / cgb < rpc * OW) {
-    int next = cgb - 1;
-    while (CG % next != 0) --next;
-    cgb = next;
-  }
-  p.rpc = rpc;
-  p.cpi = (OH + rpc - 1) / rpc;
-  p.chunks = B * p.cpi;
-  p.cgb = cgb;
-  p.ncb = CG / cgb;
-  return p;
 }
 
 }  // namespace
@@ -558,7 +468,7 @@ extern "C" {
 
 int xpt_dwconv_bn_swish_chunks(int B, int OH, int OW, int C) {
   if (B <= 0 || OH <= 0 || OW <= 0 || C <= 0 || C % 8 != 0) return 0;
-  return ef_plan(B, OH, OW, C).chunks;
+  return dw_plan(B, OH, OW, C, EF_MAX_CGB).chunks;
 }
 
 int xpt_dwconv_bn_swish_fwd(const void* x, const float* w, const float* gamma, const float* beta, const float* mean,
@@ -566,11 +476,11 @@ int xpt_dwconv_bn_swish_fwd(const void* x, const float* w, const float* gamma, c
                             int C, int k, int stride, int pad_t, int pad_l, int OH, int OW, int act_in, void* stream) {
   XPT_CHECK_PTR(x); XPT_CHECK_PTR(w); XPT_CHECK_PTR(gamma); XPT_CHECK_PTR(beta); XPT_CHECK_PTR(mean); XPT_CHECK_PTR(var);
   XPT_CHECK_PTR(v); XPT_CHECK_PTR(pool_partials);
-  const EfDims d{B, H, W, C, OH, OW, pad_t, pad_l};
-  const int rc = ef_check(d, k, stride);
+  const DwDims d{B, H, W, C, OH, OW, pad_t, pad_l};
+  const int rc = dw_check(d, k, stride);
   if (rc != XPT_OK) return rc;
-  if (!ef_aligned(x) || !ef_aligned(v) || !ef_aligned(w)) return XPT_ERR_ARG;
-  const EfPlan p = ef_plan(B, OH, OW, C);
+  if (!dw_aligned(x) || !dw_aligned(v) || !dw_aligned(w)) return XPT_ERR_ARG;
+  const DwPlan p = dw_plan(B, OH, OW, C, EF_MAX_CGB);
   if (pool_floats < (size_t)p.chunks * (size_t)C) return XPT_ERR_WORKSPACE;
   const unsigned nunits = (unsigned)p.chunks * (unsigned)p.ncb;
   const int on = g_xpt_xcd_affinity;
@@ -603,7 +513,7 @@ int xpt_se_excite_fwd(const float* pool_partials, int chunks_per_image, int HW, 
   if (B <= 0 || C <= 0 || S <= 0 || chunks_per_image <= 0 || HW <= 0) return XPT_ERR_SHAPE;
   if (C % 8 != 0) return XPT_ERR_ARG;
   if ((long long)C + S > EF_LDS_FLOATS) return XPT_ERR_SHAPE;
-  if (!ef_aligned(gate)) return XPT_ERR_ARG;                            // (read with 16-byte loads by the scale and backward kernels)
+  if (!dw_aligned(gate)) return XPT_ERR_ARG;                            // (read with 16-byte loads by the scale and backward kernels)
   XPT_BEGIN_LAUNCH();
   hipLaunchKernelGGL(ef_excite_fwd_kernel, dim3(B), dim3(256), (size_t)(C + S) * sizeof(float), (hipStream_t)stream,
                      pool_partials, chunks_per_image, 1.0f / (float)HW, w_reduce, b_reduce, w_expand, b_expand, p, r, gate, C, S);
@@ -614,7 +524,7 @@ int xpt_se_scale_fwd(const void* v, const float* gate, void* z, int B, int OH, i
   XPT_CHECK_PTR(v); XPT_CHECK_PTR(gate); XPT_CHECK_PTR(z);
   const int rc = ef_check_map(B, OH, OW, C);
   if (rc != XPT_OK) return rc;
-  if (!ef_aligned(v) || !ef_aligned(z) || !ef_aligned(gate)) return XPT_ERR_ARG;
+  if (!dw_aligned(v) || !dw_aligned(z) || !dw_aligned(gate)) return XPT_ERR_ARG;
   const unsigned CG = (unsigned)C / 8u, total = (unsigned)B * (unsigned)OH * (unsigned)OW * CG;
   const unsigned nunits = (total + 255u) / 256u;
   const int on = g_xpt_xcd_affinity;
@@ -631,8 +541,8 @@ int xpt_se_scale_bwd_reduce(const void* v, const void* dz, long long dz_pitch, f
   if (rc != XPT_OK) return rc;
   if (dz_pitch < C || dz_pitch % 8 != 0) return XPT_ERR_SHAPE;
   if ((((long long)B * OH * OW - 1) * dz_pitch + C) * 2 >= (1LL << 31)) return XPT_ERR_SHAPE;
-  if (!ef_aligned(v) || !ef_aligned(dz)) return XPT_ERR_ARG;
-  const EfPlan p = ef_plan(B, OH, OW, C);
+  if (!dw_aligned(v) || !dw_aligned(dz)) return XPT_ERR_ARG;
+  const DwPlan p = dw_plan(B, OH, OW, C, EF_MAX_CGB);
   if (partial_floats < (size_t)p.chunks * (size_t)C) return XPT_ERR_WORKSPACE;
   const unsigned nunits = (unsigned)p.chunks * (unsigned)p.ncb;
   const int on = g_xpt_xcd_affinity;
@@ -653,7 +563,7 @@ int xpt_se_excite_bwd(const float* dgate, const float* gate, const float* p, con
   if (B <= 0 || C <= 0 || S <= 0) return XPT_ERR_SHAPE;
   if (C % 8 != 0) return XPT_ERR_ARG;
   if (2LL * B * S > EF_LDS_FLOATS) return XPT_ERR_SHAPE;
-  if (!ef_aligned(dp)) return XPT_ERR_ARG;                              // (read with 16-byte loads by the depthwise backward)
+  if (!dw_aligned(dp)) return XPT_ERR_ARG;                              // (read with 16-byte loads by the depthwise backward)
   XPT_BEGIN_LAUNCH();
   hipLaunchKernelGGL(ef_excite_bwd_kernel, dim3((C + EF_CB - 1) / EF_CB), dim3(256), (size_t)2 * B * S * sizeof(float),
                      (hipStream_t)stream, dgate, gate, p, r, w_reduce, w_expand, dw_reduce, db_reduce, dw_expand, db_expand, dp, B,
@@ -667,17 +577,17 @@ int xpt_dwconv_bn_swish_bwd(const void* x, const void* v, const void* dz, long l
                             int pad_l, int OH, int OW, int act_in, void* stream) {
   XPT_CHECK_PTR(x); XPT_CHECK_PTR(v); XPT_CHECK_PTR(dz); XPT_CHECK_PTR(gate); XPT_CHECK_PTR(dp); XPT_CHECK_PTR(w);
   XPT_CHECK_PTR(gamma); XPT_CHECK_PTR(mean); XPT_CHECK_PTR(var); XPT_CHECK_PTR(partials);
-  const EfDims d{B, H, W, C, OH, OW, pad_t, pad_l};
-  const int rc = ef_check(d, k, stride);
+  const DwDims d{B, H, W, C, OH, OW, pad_t, pad_l};
+  const int rc = dw_check(d, k, stride);
   if (rc != XPT_OK) return rc;
   if (dz_pitch < C || dz_pitch % 8 != 0) return XPT_ERR_SHAPE;
   const long long opix = (long long)B * OH * OW;
   const long long dzbytes = ((opix - 1) * dz_pitch + C) * 2, vbytes = opix * C * 2;
   if (dzbytes >= (1LL << 31)) return XPT_ERR_SHAPE;
-  if (!ef_aligned(x) || !ef_aligned(v) || !ef_aligned(dz) || !ef_aligned(w) || !ef_aligned(gate) || !ef_aligned(dp)
-      || (dx != nullptr && !ef_aligned(dx)))
+  if (!dw_aligned(x) || !dw_aligned(v) || !dw_aligned(dz) || !dw_aligned(w) || !dw_aligned(gate) || !dw_aligned(dp)
+      || (dx != nullptr && !dw_aligned(dx)))
     return XPT_ERR_ARG;
-  const EfPlan p = ef_plan(B, OH, OW, C);
+  const DwPlan p = dw_plan(B, OH, OW, C, EF_MAX_CGB);
   if (partial_floats < (size_t)p.chunks * (size_t)(k * k + 2) * (size_t)C) return XPT_ERR_WORKSPACE;
   const unsigned nunits = (unsigned)p.chunks * (unsigned)p.ncb;
   const int on = g_xpt_xcd_affinity;

@@ -11,49 +11,25 @@
 //   u     = sum_{ky,kx<3} w[c,ky,kx] a(x[b, oy S + ky - pad_t, ox S + kx - pad_l, c])        (zero outside the input)
 //   y     = clamp(s[c] u + t[c], 0, 6),   s = gamma rsqrt(var + eps),  t = beta - mean s        (moving statistics)
 //
-// Activations NHWC in the 16-bit format of the build, parameters and accumulation fp32.  A lane owns 8 channels (16 bytes) of
-// a pixel; every activation access is one 16-byte buffer load whose range check supplies the zeros of the halo (an offset marker
-// past the buffer: no per-tap branch, no mask arithmetic on the values), stride / act_in / the 3x3 extent are template
-// parameters, index splits go through xpt_divmod.  At batch 8 these launches are a few hundred workgroups at one wave per SIMD
-// ("the lesson of the round"): the plans below first of all keep the workgroup count up -- on the 1/16 and
-// 1/32 maps (<= 4 x 13 pixels, 576 - 960 channels) by spreading over channel groups instead of rows.  Workgroups are numbered
-// image-major through xpt_xcd_unit, as every encoder launch is.
+// Activations NHWC in the 16-bit format of the build, parameters and accumulation fp32; the 16-byte loads and their halo are
+// those of xpt_dwstage.h, stride / act_in / the 3x3 extent are template parameters, index splits go through xpt_divmod.  At
+// batch 8 these launches are a few hundred workgroups at one wave per SIMD ("the lesson of the round"): the
+// plans first of all keep the workgroup count up -- on the 1/16 and 1/32 maps (<= 4 x 13 pixels, 576 - 960 channels) by
+// spreading over channel groups instead of rows.  Workgroups are numbered image-major through xpt_xcd_unit, as every encoder
+// launch is.
 //
 // Backward, ONE launch: re-indexed over the INPUT pixel.  The lane of input pixel p gathers gz = dy [0 < y < 6] at the (up to 9)
 // outputs that read p; with them dx(p) = a'(x) s sum_k w_k gz_k, and the same gz_k times a(x(p)) are p's contributions to
 // G[c,k] = sum gz a(x)[tap k].  dbeta's sum of gz takes the centre tap, which every output has exactly once (the entry point
 // checks that the centre of every window lies inside the input).  No atomics: a workgroup owns a chunk of input rows and a block
 // of channel groups, adds its lanes through LDS in a fixed order and writes one row of the partial matrix.
-#include "xpt_common.h"
+#include "xpt_dwstage.h"
 
 namespace {
-
-typedef unsigned int mb_u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr unsigned MB_OOB = 0x80000000u;        // byte offset no buffer of < 2^31 bytes contains: the load returns zeros
-
-struct MbDims {
-  int B, H, W, C, OH, OW, pad_t, pad_l;
-};
 
 template <int ACT>
 __device__ __forceinline__ float mb_act(float v) {
   return ACT ? fminf(fmaxf(v, 0.f), 6.f) : v;
-}
-
-__device__ __forceinline__ void mb_unpack(const mb_u32x4& v, float (&f)[8]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    f[2 * i] = xpt_h2f_lo(v[i]);
-    f[2 * i + 1] = xpt_h2f_hi(v[i]);
-  }
-}
-
-__device__ __forceinline__ uint4 mb_pack(const float (&f)[8]) {
-  unsigned p[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) p[i] = (unsigned)xpt_f2h(f[2 * i]) | ((unsigned)xpt_f2h(f[2 * i + 1]) << 16);
-  return make_uint4(p[0], p[1], p[2], p[3]);
 }
 
 // the 72 weights [8 channels][9 taps] of channel group cg (288 bytes, 16-byte aligned) and the BatchNorm scale of its channels
@@ -72,7 +48,7 @@ template <int S, int ACT, int OXT>
 __global__ __launch_bounds__(256) void mb_fwd_kernel(const void* __restrict__ x, const float* __restrict__ w,
                                                       const float* __restrict__ gamma, const float* __restrict__ beta,
                                                       const float* __restrict__ mean, const float* __restrict__ var, float eps,
-                                                      void* __restrict__ y, MbDims d, unsigned xbytes, unsigned nunits,
+                                                      void* __restrict__ y, DwDims d, unsigned xbytes, unsigned nunits,
                                                       unsigned total, unsigned CG, unsigned OXB, int xcd_on) {
   unsigned unit;
   if (!xpt_xcd_unit(xcd_on != 0, blockIdx.x, nunits, unit)) return;
@@ -107,18 +83,18 @@ __global__ __launch_bounds__(256) void mb_fwd_kernel(const void* __restrict__ x,
   for (int ky = 0; ky < 3; ++ky) {
     const int iy = iy0 + ky;
     const bool rowok = (unsigned)iy < (unsigned)d.H;
-    mb_u32x4 v[NC];
+    dw_u32x4 v[NC];
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       const int ix = ix0 + c;
       const bool ok = rowok && (unsigned)ix < (unsigned)d.W;
-      const unsigned off = ok ? base + (unsigned)iy * rowpitch + (unsigned)ix * pix : MB_OOB;
+      const unsigned off = ok ? base + (unsigned)iy * rowpitch + (unsigned)ix * pix : DW_OOB;
       v[c] = __builtin_amdgcn_raw_buffer_load_b128(rx, off, 0, 0);
     }
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
       float a[8];
-      mb_unpack(v[c], a);
+      dw_unpack(v[c], a);
 #pragma unroll
       for (int j = 0; j < 8; ++j) a[j] = mb_act<ACT>(a[j]);
 #pragma unroll
@@ -139,38 +115,24 @@ __global__ __launch_bounds__(256) void mb_fwd_kernel(const void* __restrict__ x,
 #pragma unroll
       for (int j = 0; j < 8; ++j) r[j] = fminf(fmaxf(sc[j] * acc[o][j] + sh[j], 0.f), 6.f);
       const size_t e = ((size_t)(b * (unsigned)d.OH + oy) * (unsigned)d.OW + ox) * (unsigned)d.C + cg * 8u;
-      *(uint4*)((unsigned short*)y + e) = mb_pack(r);
+      *(uint4*)((unsigned short*)y + e) = dw_pack(r);
     }
   }
 }
 
 // ------------------------------------------------------------------------------------------------ backward
-struct MbBwdPlan {
-  int rpc;       // output rows per chunk
-  int cpi;       // chunks per image
-  int chunks;    // B * cpi: rows of the partial matrix
-  int cgb;       // channel groups per workgroup (a divisor of C / 8, <= 64)
-  int ncb;       // channel blocks: (C / 8) / cgb
-};
-
-// first input row of the chunk that starts at output row oy: the chunks of an image tile its input rows [0, H)
-__device__ __forceinline__ int mb_in_row(int oy, int S, int OH, int H) {
-  return oy <= 0 ? 0 : (oy >= OH ? H : min(H, oy * S));
-}
-
 constexpr int MB_NE = 11;                 // per channel: 9 weight-gradient entries, dgamma, dbeta
-constexpr int MB_PASS = 4;                // entries per LDS pass of the workgroup sum
-
+constexpr int MB_MAX_CGB = 64;            // channel groups per workgroup at most
 // workgroup = (chunk, channel block cb); thread = (pl, cgl): channel group cb cgb + cgl, input pixels pl, pl + PXT, ... of the chunk
 template <int S, int ACT>
 __global__ __launch_bounds__(256) void mb_bwd_kernel(const void* __restrict__ x, const void* __restrict__ y,
                                                       const void* __restrict__ dy, unsigned dy_pitch_bytes,
                                                       const float* __restrict__ w, const float* __restrict__ gamma,
                                                       const float* __restrict__ mean, const float* __restrict__ var, float eps,
-                                                      void* __restrict__ dx, float* __restrict__ partials, MbDims d, MbBwdPlan p,
+                                                      void* __restrict__ dx, float* __restrict__ partials, DwDims d, DwPlan p,
                                                       unsigned ybytes,
                                                       unsigned dybytes, unsigned nunits, int xcd_on) {
-  __shared__ float red[MB_PASS * 8][256];
+  __shared__ float red[DW_PASS * 8][256];
   unsigned unit;
   if (!xpt_xcd_unit(xcd_on != 0, blockIdx.x, nunits, unit)) return;          // (uniform over the workgroup)
   unsigned cb;
@@ -178,7 +140,7 @@ __global__ __launch_bounds__(256) void mb_bwd_kernel(const void* __restrict__ x,
   unsigned oyc;
   const unsigned b = xpt_divmod(chunk, (unsigned)p.cpi, oyc);
   const int oy0 = (int)oyc * p.rpc, oy1 = min(d.OH, oy0 + p.rpc);
-  const int r0 = mb_in_row(oy0, S, d.OH, d.H), r1 = mb_in_row(oy1, S, d.OH, d.H);
+  const int r0 = dw_in_row(oy0, S, d.OH, d.H), r1 = dw_in_row(oy1, S, d.OH, d.H);
   const unsigned npix = (unsigned)(r1 - r0) * (unsigned)d.W;
   const unsigned CGB = (unsigned)p.cgb, PXT = 256u / CGB;
   unsigned cgl;
@@ -211,17 +173,15 @@ __global__ __launch_bounds__(256) void mb_bwd_kernel(const void* __restrict__ x,
       unsigned ix;
       const int iy = r0 + (int)xpt_divmod(i, (unsigned)d.W, ix);
       const size_t xe = ((size_t)(b * (unsigned)d.H + (unsigned)iy) * (unsigned)d.W + ix) * (unsigned)d.C + cg * 8u;
-      const uint4 xv4 = *(const uint4*)((const unsigned short*)x + xe);
-      const mb_u32x4 xv = {xv4.x, xv4.y, xv4.z, xv4.w};
       float xa[8], live[8];
-      mb_unpack(xv, xa);
+      dw_unpack(dw_load16(x, xe), xa);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         live[j] = (!ACT || (xa[j] > 0.f && xa[j] < 6.f)) ? 1.f : 0.f;
         xa[j] = mb_act<ACT>(xa[j]);
       }
       // the outputs that read this pixel: tap (ky, kx) of output ((iy + pad_t - ky) / S, (ix + pad_l - kx) / S)
-      mb_u32x4 vy[9], vd[9];
+      dw_u32x4 vy[9], vd[9];
 #pragma unroll
       for (int ky = 0; ky < 3; ++ky) {
         const int ty = iy + d.pad_t - ky;
@@ -233,8 +193,8 @@ __global__ __launch_bounds__(256) void mb_bwd_kernel(const void* __restrict__ x,
           const int ox = S == 2 ? tx >> 1 : tx;
           const bool ok = yok && tx >= 0 && (S == 1 || (tx & 1) == 0) && ox < d.OW;
           const unsigned opix = (b * (unsigned)d.OH + (unsigned)oy) * (unsigned)d.OW + (unsigned)ox;
-          vy[ky * 3 + kx] = __builtin_amdgcn_raw_buffer_load_b128(ry, ok ? opix * pix + cg * 16u : MB_OOB, 0, 0);
-          vd[ky * 3 + kx] = __builtin_amdgcn_raw_buffer_load_b128(rd, ok ? opix * dy_pitch_bytes + cg * 16u : MB_OOB, 0, 0);
+          vy[ky * 3 + kx] = __builtin_amdgcn_raw_buffer_load_b128(ry, ok ? opix * pix + cg * 16u : DW_OOB, 0, 0);
+          vd[ky * 3 + kx] = __builtin_amdgcn_raw_buffer_load_b128(rd, ok ? opix * dy_pitch_bytes + cg * 16u : DW_OOB, 0, 0);
         }
       }
       float ds[8];
@@ -243,8 +203,8 @@ __global__ __launch_bounds__(256) void mb_bwd_kernel(const void* __restrict__ x,
 #pragma unroll
       for (int k = 0; k < 9; ++k) {
         float yv[8], gz[8];
-        mb_unpack(vy[k], yv);
-        mb_unpack(vd[k], gz);
+        dw_unpack(vy[k], yv);
+        dw_unpack(vd[k], gz);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           gz[j] = (yv[j] > 0.f && yv[j] < 6.f) ? gz[j] : 0.f;          // tf.nn.relu6: no gradient at exactly 0 and 6
@@ -257,7 +217,7 @@ __global__ __launch_bounds__(256) void mb_bwd_kernel(const void* __restrict__ x,
         float r[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) r[j] = live[j] * sc[j] * ds[j];
-        *(uint4*)((unsigned short*)dx + xe) = mb_pack(r);
+        *(uint4*)((unsigned short*)dx + xe) = dw_pack(r);
       }
     }
   }
@@ -279,12 +239,12 @@ __global__ __launch_bounds__(256) void mb_bwd_kernel(const void* __restrict__ x,
   // the workgroup's sum over pl, in pl order; row `chunk` of the partial matrix: [C][9] weights | [C] gamma | [C] beta
   float* prow = partials + (size_t)chunk * MB_NE * (unsigned)d.C;
 #pragma unroll
-  for (int pass = 0; pass < (MB_NE + MB_PASS - 1) / MB_PASS; ++pass) {
+  for (int pass = 0; pass < (MB_NE + DW_PASS - 1) / DW_PASS; ++pass) {
     __syncthreads();                                                     // the previous pass has been read
     if (active) {
 #pragma unroll
-      for (int el = 0; el < MB_PASS; ++el) {
-        const int e = pass * MB_PASS + el;
+      for (int el = 0; el < DW_PASS; ++el) {
+        const int e = pass * DW_PASS + el;
         if (e < MB_NE) {
 #pragma unroll
           for (int j = 0; j < 8; ++j) red[el * 8 + j][threadIdx.x] = out[e][j];
@@ -292,14 +252,14 @@ __global__ __launch_bounds__(256) void mb_bwd_kernel(const void* __restrict__ x,
       }
     }
     __syncthreads();
-    const int ne = min(MB_PASS, MB_NE - pass * MB_PASS);
+    const int ne = min(DW_PASS, MB_NE - pass * DW_PASS);
     const unsigned nout = (unsigned)ne * 8u * CGB;
     for (unsigned o = threadIdx.x; o < nout; o += 256u) {
       unsigned gl;
       const unsigned v = xpt_divmod(o, CGB, gl);                         // v = el * 8 + j
       float sum = 0.f;
       for (unsigned t = 0; t < PXT; ++t) sum += red[v][t * CGB + gl];
-      const unsigned e = (unsigned)pass * MB_PASS + (v >> 3), c = (cb * CGB + gl) * 8u + (v & 7u);
+      const unsigned e = (unsigned)pass * DW_PASS + (v >> 3), c = (cb * CGB + gl) * 8u + (v & 7u);
       const unsigned at = e < 9u ? c * 9u + e : (e * (unsigned)d.C + c);   // 9 C + c (gamma), 10 C + c (beta)
       prow[at] = sum;
     }
@@ -307,47 +267,9 @@ __global__ __launch_bounds__(256) void mb_bwd_kernel(const void* __restrict__ x,
 }
 
 // ------------------------------------------------------------------------------------------------ host side
-int mb_check(const MbDims& d, int stride) {
-  if (d.B <= 0 || d.H <= 0 || d.W <= 0 || d.C <= 0 || d.OH <= 0 || d.OW <= 0) return XPT_ERR_SHAPE;
-  if (d.C % 8 != 0) return XPT_ERR_ARG;                                  // 16-byte channel groups
-  if (stride != 1 && stride != 2) return XPT_ERR_ARG;
-  if (d.pad_t < 0 || d.pad_t > 1 || d.pad_l < 0 || d.pad_l > 1) return XPT_ERR_ARG;
-  // the centre of every window inside the input (SAME padding of a 3x3 window, either stride, any parity)
-  if ((long long)(d.OH - 1) * stride + 1 - d.pad_t > d.H - 1 || (long long)(d.OW - 1) * stride + 1 - d.pad_l > d.W - 1)
-    return XPT_ERR_SHAPE;
-  // 32-bit byte offsets below the out-of-range marker, 32-bit item numbers
-  if ((long long)d.B * d.H * d.W * d.C * 2 >= (1LL << 31)) return XPT_ERR_SHAPE;
-  return XPT_OK;
-}
-
-bool mb_aligned(const void* p) { return ((uintptr_t)p & 15u) == 0; }
-
-MbBwdPlan mb_bwd_plan(int B, int OH, int OW, int C) {
-  MbBwdPlan p;
-  const int CG = C / 8;
-  int cgb = 1;
-  for (int dv = 1; dv <= 64 && dv <= CG; ++dv)
-    if (CG % dv == 0) cgb = dv;
-  auto groups = [&](int rpc, int g) { return (long long)B * ((OH + rpc - 1) / rpc) * (CG / g); };
-  int rpc = 1;
-  while (rpc < OH && groups(rpc, cgb) > 2048) rpc *= 2;
-  // few workgroups (the 1/16 and 1/32 maps): spread over channel groups, down to one lane row per output pixel of the chunk
-  while (cgb > 1 && groups(rpc, cgb) < 512 && 256 / cgb < rpc * OW) {
-    int next = cgb - 1;
-    while (CG % next != 0) --next;
-    cgb = next;
-  }
-  p.rpc = rpc;
-  p.cpi = (OH + rpc - 1) / rpc;
-  p.chunks = B * p.cpi;
-  p.cgb = cgb;
-  p.ncb = CG / cgb;
-  return p;
-}
-
 template <int S, int ACT, int OXT>
 void mb_launch_fwd(const void* x, const float* w, const float* gamma, const float* beta, const float* mean, const float* var,
-                   float eps, void* y, const MbDims& d, hipStream_t stream) {
+                   float eps, void* y, const DwDims& d, hipStream_t stream) {
   const unsigned CG = (unsigned)d.C / 8u, OXB = ((unsigned)d.OW + OXT - 1) / OXT;
   const unsigned total = (unsigned)d.B * (unsigned)d.OH * OXB * CG;
   const unsigned nunits = (total + 255u) / 256u;
@@ -371,7 +293,7 @@ int mb_fwd_outputs(int B, int OH, int OW, int C) {
 
 template <int S, int ACT>
 void mb_dispatch_fwd(const void* x, const float* w, const float* gamma, const float* beta, const float* mean, const float* var,
-                     float eps, void* y, const MbDims& d, hipStream_t stream) {
+                     float eps, void* y, const DwDims& d, hipStream_t stream) {
   const int oxt = mb_fwd_outputs(d.B, d.OH, d.OW, d.C);
   if (oxt == 4) mb_launch_fwd<S, ACT, 4>(x, w, gamma, beta, mean, var, eps, y, d, stream);
   else if (oxt == 2) mb_launch_fwd<S, ACT, 2>(x, w, gamma, beta, mean, var, eps, y, d, stream);
@@ -387,10 +309,10 @@ int xpt_dwconv_bn_relu6_fwd(const void* x, const float* w, const float* gamma, c
                             int OH, int OW, int act_in, void* stream) {
   XPT_CHECK_PTR(x); XPT_CHECK_PTR(w); XPT_CHECK_PTR(gamma); XPT_CHECK_PTR(beta); XPT_CHECK_PTR(mean); XPT_CHECK_PTR(var);
   XPT_CHECK_PTR(y);
-  const MbDims d{B, H, W, C, OH, OW, pad_t, pad_l};
-  const int rc = mb_check(d, stride);
+  const DwDims d{B, H, W, C, OH, OW, pad_t, pad_l};
+  const int rc = dw_check(d, 3, stride);
   if (rc != XPT_OK) return rc;
-  if (!mb_aligned(x) || !mb_aligned(y) || !mb_aligned(w)) return XPT_ERR_ARG;
+  if (!dw_aligned(x) || !dw_aligned(y) || !dw_aligned(w)) return XPT_ERR_ARG;
   const hipStream_t s = (hipStream_t)stream;
   XPT_BEGIN_LAUNCH();
   if (stride == 1) {
@@ -416,7 +338,7 @@ int xpt_dwconv_bn_relu6_fwd_outputs(int B, int OH, int OW, int C) {
 
 int xpt_dwconv_bn_relu6_bwd_chunks(int B, int OH, int OW, int C) {
   if (B <= 0 || OH <= 0 || OW <= 0 || C <= 0 || C % 8 != 0) return 0;
-  return mb_bwd_plan(B, OH, OW, C).chunks;
+  return dw_plan(B, OH, OW, C, MB_MAX_CGB).chunks;
 }
 
 int xpt_dwconv_bn_relu6_bwd(const void* x, const void* y, const void* dy, long long dy_pitch, const float* w,
@@ -426,16 +348,16 @@ int xpt_dwconv_bn_relu6_bwd(const void* x, const void* y, const void* dy, long l
   XPT_CHECK_PTR(x); XPT_CHECK_PTR(y); XPT_CHECK_PTR(dy); XPT_CHECK_PTR(w); XPT_CHECK_PTR(gamma); XPT_CHECK_PTR(mean);
   XPT_CHECK_PTR(var);
   XPT_CHECK_PTR(partials);
-  const MbDims d{B, H, W, C, OH, OW, pad_t, pad_l};
-  const int rc = mb_check(d, stride);
+  const DwDims d{B, H, W, C, OH, OW, pad_t, pad_l};
+  const int rc = dw_check(d, 3, stride);
   if (rc != XPT_OK) return rc;
   if (dy_pitch < C || dy_pitch % 8 != 0) return XPT_ERR_SHAPE;
   const long long opix = (long long)B * OH * OW;
   const long long dybytes = ((opix - 1) * dy_pitch + C) * 2, ybytes = opix * C * 2;
   if (dybytes >= (1LL << 31) || ybytes >= (1LL << 31)) return XPT_ERR_SHAPE;
-  if (!mb_aligned(x) || !mb_aligned(y) || !mb_aligned(dy) || !mb_aligned(w) || (dx != nullptr && !mb_aligned(dx)))
+  if (!dw_aligned(x) || !dw_aligned(y) || !dw_aligned(dy) || !dw_aligned(w) || (dx != nullptr && !dw_aligned(dx)))
     return XPT_ERR_ARG;
-  const MbBwdPlan p = mb_bwd_plan(B, OH, OW, C);
+  const DwPlan p = dw_plan(B, OH, OW, C, MB_MAX_CGB);
   if (partial_floats < (size_t)p.chunks * MB_NE * (size_t)C) return XPT_ERR_WORKSPACE;
   const unsigned nunits = (unsigned)p.chunks * (unsigned)p.ncb;
   const int on = g_xpt_xcd_affinity;

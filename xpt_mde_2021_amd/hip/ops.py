@@ -892,12 +892,35 @@ def multi_depthwise(inputs, weights, relu_in=True, stride=1, pads=None):
 
 
 # ------------------------------------------------------------------------------- MobileNetV2 depthwise stage
-def _same_pads3(h, w, stride):
-    """(top, left) zeros and output size of a 3x3 window with TF SAME padding (= keras correct_pad + valid at stride 2)."""
-    if stride == 1:
-        return 1, 1, h, w
-    oh, ow = -(-h // 2), -(-w // 2)
-    return ((oh - 1) * 2 + 3 - h) // 2, ((ow - 1) * 2 + 3 - w) // 2, oh, ow
+def _same_pads(h, w, k, stride):
+    """(top, left) zeros and output size of a k x k window with TF SAME padding (= keras correct_pad + valid at stride 2)."""
+    oh, ow = -(-h // stride), -(-w // stride)
+    return max((oh - 1) * stride + k - h, 0) // 2, max((ow - 1) * stride + k - w, 0) // 2, oh, ow
+
+
+def _f32_param(op, name, t, n, what="tensor"):
+    if t.dtype != torch.float32 or not t.is_cuda or t.numel() != n or not t.is_contiguous():
+        raise _lib.XptHipError(f"{op}: {name} must be a contiguous float32 CUDA {what} of {n} elements")
+    return t
+
+
+def _rows_for_16_byte_loads(t):
+    """_rows_with_pitch, with a channels_last copy of a slice the 16-byte loads cannot take in place."""
+    rows, pitch = _rows_with_pitch(t)
+    if pitch % 8 or rows.data_ptr() % 16:
+        rows, pitch = rows.contiguous(memory_format=torch.channels_last), t.shape[1]
+    return rows, pitch
+
+
+def _partial_rows(op, sink_dst, key, n, device):
+    """n floats for a backward's partial rows: the GradSink's when the gradients go to flat destinations, else a workspace the
+    backward sums itself -- which a graph capture cannot do."""
+    if sink_dst is not None:
+        return grad_sink.partials(sink_dst, key, n)
+    if torch.cuda.is_current_stream_capturing():
+        # (torch.sum inside a captured step: a memset node this runtime replays wrongly, DESIGN.md section 6)
+        raise _lib.XptHipError(f"{op} backward without flat-gradient destinations inside a graph capture")
+    return torch.empty(n, dtype=torch.float32, device=device)
 
 
 class _DwBnRelu6(torch.autograd.Function):
@@ -911,9 +934,8 @@ class _DwBnRelu6(torch.autograd.Function):
         w = weight.detach().contiguous()
         g_, b_ = gamma.detach().contiguous(), beta.detach().contiguous()
         for name, t, n in (("weight", w, 9 * C), ("gamma", g_, C), ("beta", b_, C), ("mean", mean, C), ("var", var, C)):
-            if t.dtype != torch.float32 or not t.is_cuda or t.numel() != n or not t.is_contiguous():
-                raise _lib.XptHipError(f"dwconv_bn_relu6: {name} must be a contiguous float32 CUDA tensor of {n} elements")
-        pt, pl, OH, OW = _same_pads3(H, W, stride)
+            _f32_param("dwconv_bn_relu6", name, t, n)
+        pt, pl, OH, OW = _same_pads(H, W, 3, stride)
         y = torch.empty((B, C, OH, OW), dtype=x.dtype, device=x.device, memory_format=torch.channels_last)
         _lib.check(lib.xpt_dwconv_bn_relu6_fwd(_ptr(x), _ptr(w), _ptr(g_), _ptr(b_), _ptr(mean), _ptr(var), float(eps), _ptr(y),
                                                B, H, W, C, stride, pt, pl, OH, OW, int(act_in), _stream()),
@@ -931,19 +953,11 @@ class _DwBnRelu6(torch.autograd.Function):
         x, y, w, gamma, mean, var = ctx.saved_tensors
         eps, stride, pt, pl, OH, OW, act_in, wshape = ctx.cfg
         B, C, H, W = x.shape
-        dy, pitch = _rows_with_pitch(dy_in.to(x.dtype))
-        if pitch % 8 or dy.data_ptr() % 16:                      # (a slice the 16-byte loads cannot take in place)
-            dy, pitch = dy.contiguous(memory_format=torch.channels_last), C
+        dy, pitch = _rows_for_16_byte_loads(dy_in.to(x.dtype))
         dx = torch.empty_like(x, memory_format=torch.channels_last) if ctx.needs_input_grad[0] else None
         nchunk = lib.xpt_dwconv_bn_relu6_bwd_chunks(B, OH, OW, C)
         row = 11 * C
-        if ctx.sink_dst is not None:
-            ws = grad_sink.partials(ctx.sink_dst[0], "mbconv", nchunk * row)
-        elif torch.cuda.is_current_stream_capturing():
-            # (torch.sum inside a captured step: a memset node this runtime replays wrongly)
-            raise _lib.XptHipError("dwconv_bn_relu6 backward without flat-gradient destinations inside a graph capture")
-        else:
-            ws = torch.empty(nchunk * row, dtype=torch.float32, device=x.device)
+        ws = _partial_rows("dwconv_bn_relu6", ctx.sink_dst and ctx.sink_dst[0], "mbconv", nchunk * row, x.device)
         _lib.check(lib.xpt_dwconv_bn_relu6_bwd(_ptr(x), _ptr(y), _ptr(dy), pitch, _ptr(w), _ptr(gamma), _ptr(mean), _ptr(var),
                                                eps, _ptr(dx), _ptr(ws), ws.numel(), B, H, W, C, stride, pt, pl, OH, OW, act_in,
                                                _stream()), "xpt_dwconv_bn_relu6_bwd")
@@ -978,7 +992,7 @@ def dwconv_bn_relu6_torch(x, weight, bn, stride=1, act_in=False, eps=1e-3):
     import torch.nn.functional as F
     a = F.relu6(x) if act_in else x                    # (hardtanh: no gradient at exactly 0 and 6, as tf.nn.relu6)
     H, W = x.shape[2:]
-    pt, pl, OH, OW = _same_pads3(H, W, stride)
+    pt, pl, OH, OW = _same_pads(H, W, 3, stride)
     if stride == 2:                                    # ZeroPadding2D(correct_pad) + "valid"
         a = F.pad(a, (pl, (OW - 1) * 2 + 3 - W - pl, pt, (OH - 1) * 2 + 3 - H - pt))
     u = F.conv2d(a, weight.to(a.dtype), None, stride, 1 if stride == 1 else 0, 1, x.shape[1])
@@ -988,12 +1002,6 @@ def dwconv_bn_relu6_torch(x, weight, bn, stride=1, act_in=False, eps=1e-3):
 
 
 # ------------------------------------------------------------------------------- EfficientNet MBConv middle
-def _same_pads(h, w, k, stride):
-    """(top, left) zeros and output size of a k x k window with TF SAME padding (= keras correct_pad + valid at stride 2)."""
-    oh, ow = -(-h // stride), -(-w // stride)
-    return max((oh - 1) * stride + k - h, 0) // 2, max((ow - 1) * stride + k - w, 0) // 2, oh, ow
-
-
 class _MbconvSE(torch.autograd.Function):
     """depthwise k x k -> BatchNorm -> swish -> squeeze-and-excite -> multiply on the kernels of csrc/xpt_effconv.hip: three
     launches forward (depthwise stage with pool partials, excite, scale), four backward (dL/dgate rows and their finish, excite
@@ -1009,8 +1017,7 @@ class _MbconvSE(torch.autograd.Function):
         w, g_, b_, wr_, br_, we_, be_ = (f32(t) for t in (weight, gamma, beta, wr, br, we, be))
         for name, t, n in (("dw_weight", w, k * k * C), ("gamma", g_, C), ("beta", b_, C), ("mean", mean, C), ("var", var, C),
                            ("se_reduce_w", wr_, S * C), ("se_reduce_b", br_, S), ("se_expand_w", we_, C * S), ("se_expand_b", be_, C)):
-            if t.dtype != torch.float32 or not t.is_cuda or t.numel() != n or not t.is_contiguous():
-                raise _lib.XptHipError(f"mbconv_se: {name} must be a contiguous float32 CUDA tensor of {n} elements")
+            _f32_param("mbconv_se", name, t, n)
         pt, pl, OH, OW = _same_pads(H, W, k, stride)
         nchunk = lib.xpt_dwconv_bn_swish_chunks(B, OH, OW, C)
         if nchunk <= 0:
@@ -1043,20 +1050,11 @@ class _MbconvSE(torch.autograd.Function):
         eps, k, stride, pt, pl, OH, OW, act_in, S, nchunk = ctx.cfg
         B, C, H, W = x.shape
         dev = x.device
-        dz, pitch = _rows_with_pitch(dz_in.to(x.dtype))
-        if pitch % 8 or dz.data_ptr() % 16:                      # (a slice the 16-byte loads cannot take in place)
-            dz, pitch = dz.contiguous(memory_format=torch.channels_last), C
+        dz, pitch = _rows_for_16_byte_loads(dz_in.to(x.dtype))
         row = (k * k + 2) * C
         nse = 2 * S * C + S + C                                  # [S C dW_r | S db_r | C S dW_e | C db_e]
-        if ctx.sink_dst is not None:
-            ws = grad_sink.partials(ctx.sink_dst[0], "effconv", nchunk * row)
-            se = grad_sink.partials(ctx.sink_dst[3], "effconv_se", nse)
-        elif torch.cuda.is_current_stream_capturing():
-            # (torch.sum inside a captured step: a memset node this runtime replays wrongly)
-            raise _lib.XptHipError("mbconv_se backward without flat-gradient destinations inside a graph capture")
-        else:
-            ws = torch.empty(nchunk * row, dtype=torch.float32, device=dev)
-            se = torch.empty(nse, dtype=torch.float32, device=dev)
+        ws = _partial_rows("mbconv_se", ctx.sink_dst and ctx.sink_dst[0], "effconv", nchunk * row, dev)
+        se = _partial_rows("mbconv_se", ctx.sink_dst and ctx.sink_dst[3], "effconv_se", nse, dev)
         rows = torch.empty(nchunk * C, dtype=torch.float32, device=dev)
         dgate, dp = torch.empty((B, C), dtype=torch.float32, device=dev), torch.empty((B, C), dtype=torch.float32, device=dev)
         dx = torch.empty_like(x, memory_format=torch.channels_last) if ctx.needs_input_grad[0] else None
@@ -1140,10 +1138,7 @@ def _half_weight(weight):
 
 
 def _f32_vector(t, n, name):
-    t = t.detach()
-    if t.dtype != torch.float32 or not t.is_cuda or t.numel() != n or not t.is_contiguous():
-        raise _lib.XptHipError(f"res_join: {name} must be a contiguous float32 CUDA vector of {n} elements")
-    return t
+    return _f32_param("res_join", name, t.detach(), n, "vector")
 
 
 class _ResJoin(torch.autograd.Function):
@@ -1232,13 +1227,7 @@ class _ResJoin(torch.autograd.Function):
         nblk = lib.xpt_res_join_bwd_blocks(M, N)
         if nblk < 1:
             raise _lib.XptHipError(f"xpt_res_join_bwd_blocks failed: {nblk}")
-        if ctx.sink_vec is not None:
-            ws = grad_sink.partials(ctx.sink_vec[3], "resjoin", nblk * 3 * N)
-        elif torch.cuda.is_current_stream_capturing():
-            # (torch.sum inside a captured step: a memset node this runtime replays wrongly)
-            raise _lib.XptHipError("res_join backward without flat-gradient destinations inside a graph capture")
-        else:
-            ws = torch.empty(nblk * 3 * N, dtype=torch.float32, device=out.device)
+        ws = _partial_rows("res_join", ctx.sink_vec and ctx.sink_vec[3], "resjoin", nblk * 3 * N, out.device)
         _lib.check(lib.xpt_res_join_bwd(_ptr(g_out), _ptr(g_pre), _ptr(out), _ptr(gamma), _ptr(beta), _ptr(mean), _ptr(var), eps,
                                         _ptr(g), _ptr(gs), _ptr(ws), ws.numel(), M, N, stride, OH, OW, IH, IW, _stream()),
                    "xpt_res_join_bwd")

@@ -24,6 +24,7 @@ on the same weights; every Keras variable of the no-top B0 lands on exactly one 
 own Rescaling(1/255) and Normalization layers meet images in [-1, 1]: (x / 255 - mean) / sqrt(var); BatchNorm runs on its moving
 statistics with trainable gamma / beta.  B3 / B5 / B7 are pinned on the CPU only: they have not run on hardware.
 """
+import functools
 import math
 
 import torch
@@ -32,10 +33,10 @@ import torch.nn.functional as F
 
 from ...hip import conv as _conv
 from ...hip import ops as _ops
-from ...hip.lib import half as _half
 from ...utils.util_class import WrongInputException
-from .pretrained_nets import (BN_EPS, FrozenBatchNorm, _from_keras, _to_keras, conv1x1_bn, correct_pad, read_keras_weight_file,
-                              zero_pad)
+from . import keras_weights as _kw
+from .keras_weights import _from_keras  # noqa: F401  (the layout converter stays addressable through this module)
+from .pretrained_nets import BN_EPS, FrozenBatchNorm, KerasApplicationEncoder, conv1x1_bn, correct_pad, zero_pad
 
 # (kernel, repeats, input filters, output filters, expand ratio, stride) of keras efficientnet.DEFAULT_BLOCKS_ARGS; se_ratio 0.25
 BLOCK_ARGS = ((3, 1, 32, 16, 1, 1), (3, 2, 16, 24, 6, 2), (5, 2, 24, 40, 6, 2), (3, 3, 40, 80, 6, 2), (5, 3, 80, 112, 6, 1),
@@ -59,11 +60,7 @@ def round_repeats(repeats, depth):
     return int(math.ceil(depth * repeats))
 
 
-def _he(conv):
-    nn.init.kaiming_normal_(conv.weight, mode="fan_in", nonlinearity="relu")
-    if conv.bias is not None:
-        nn.init.zeros_(conv.bias)
-    return conv
+_he = KerasApplicationEncoder.he
 
 
 class MBConv(nn.Module):
@@ -97,7 +94,7 @@ class MBConv(nn.Module):
         return conv1x1_bn(z, self.project.weight, self.project_bn, residual=x if self.use_res else None), h
 
 
-class EfficientNetEncoder(nn.Module):
+class EfficientNetEncoder(KerasApplicationEncoder):
     """Keras EfficientNetB<n>(include_top=False) with the five taps of scaled_layers.json.
 
     forward(image NCHW in [-1,1], H and W multiples of 32) -> [c1 (1/2), c2 (1/4), c3 (1/8), c4 (1/16), c5 (1/32)], all
@@ -133,10 +130,6 @@ class EfficientNetEncoder(nn.Module):
         self.out_channels = top
         self.TAP_CHANNELS = tuple(taps[b] for b in self.tap_blocks) + (top,)
 
-    def tap_layout(self):
-        """[(physical channels, logical index set or None)] of the five taps: no structurally-zero channels here."""
-        return [(c, None) for c in self.TAP_CHANNELS]
-
     def preprocess(self, image):
         """Rescaling(1/255) and Normalization(axis=3) of the Keras model, applied to the [-1, 1] image as the reference does
         (efficientnet.preprocess_input is the identity)."""
@@ -146,17 +139,14 @@ class EfficientNetEncoder(nn.Module):
     def stem(self, image):
         """stem_conv + stem_bn, pre-activation (its swish rides in block1a's depthwise loads)."""
         x = self.preprocess(image)
-        if _conv.usable(x, self.stem_conv, 1.0):                      # the matrix-core convolution: 3 -> 8 channels, 16-byte pixels
-            x = F.pad(x.to(_half()), (0, 0, 0, 0, 0, 5)).contiguous(memory_format=torch.channels_last)
-            x = _conv.conv2d_same(x, self.stem_conv.weight, None, 2, 1.0)
+        if _conv.usable(x, self.stem_conv, 1.0):
+            x = self.stem_matrix_core(x, self.stem_conv, 2)
         else:                                                         # host tensors / fp32: ZeroPadding2D(correct_pad) + valid
             x = F.conv2d(zero_pad(x, correct_pad(x.shape[2], x.shape[3], 3)), self.stem_conv.weight, None, 2)
         return self.stem_bn(x)
 
     def forward(self, image, physical_taps=False):
-        h, w = image.shape[2:]
-        if h % 32 or w % 32:
-            raise WrongInputException(f"{self.net_name} encoder: image {h} x {w} is not a multiple of 32 in both extents")
+        self.check_image(image)
         x = self.stem(image)
         taps = []
         for k, block in enumerate(self.blocks):
@@ -171,14 +161,9 @@ class EfficientNetEncoder(nn.Module):
 # ------------------------------------------------------------------------------------------ Keras weights
 def keras_variable_map(encoder):
     """{keras variable name: (tensor of the encoder, kind)} with kind in {"conv", "depthwise", "vector"}
-    (tf.keras.applications.efficientnet layer names; layouts as pretrained_nets._to_keras)."""
+    (tf.keras.applications.efficientnet layer names; layouts as keras_weights._to_keras)."""
     out = {}
-
-    def bn(name, module):
-        out[f"{name}/gamma"] = (module.weight, "vector")
-        out[f"{name}/beta"] = (module.bias, "vector")
-        out[f"{name}/moving_mean"] = (module.running_mean, "vector")
-        out[f"{name}/moving_variance"] = (module.running_var, "vector")
+    bn = functools.partial(_kw.bn, out)
 
     out["normalization/mean"] = (encoder.norm_mean, "vector")
     out["normalization/variance"] = (encoder.norm_variance, "vector")
@@ -205,28 +190,10 @@ def keras_variable_map(encoder):
 
 def export_keras_weights(encoder):
     """{keras variable name: float32 array in the keras layout} of the encoder's current weights."""
-    return {name: _to_keras(kind, t.detach()).contiguous().float().cpu() for name, (t, kind) in keras_variable_map(encoder).items()}
+    return _kw.export_weights(keras_variable_map(encoder))
 
 
 def load_keras_weights(encoder, weights):
     """Fills the encoder from Keras EfficientNetB<n>(include_top=False) variables (a path or a {name: array} dict).  Strict: a
     missing, unknown or mis-shaped variable raises; nothing is loaded partially."""
-    if not isinstance(weights, dict):
-        weights = read_keras_weight_file(weights)
-    table = keras_variable_map(encoder)
-    missing = sorted(set(table) - set(weights))
-    unknown = sorted(set(weights) - set(table))
-    if missing or unknown:
-        raise WrongInputException(f"{encoder.net_name} weights: {len(missing)} variables missing (e.g. {missing[:3]}), "
-                                  f"{len(unknown)} not part of the no-top model (e.g. {unknown[:3]})")
-    staged = {}
-    for name, (t, kind) in table.items():
-        a = torch.as_tensor(weights[name])
-        want = tuple(_to_keras(kind, t).shape)
-        if tuple(a.shape) != want:
-            raise WrongInputException(f"{name}: file has shape {tuple(a.shape)}, the model expects {want}")
-        staged[name] = _from_keras(kind, a)
-    with torch.no_grad():
-        for name, (t, kind) in table.items():
-            t.copy_(staged[name].to(device=t.device, dtype=t.dtype))
-    return len(staged)
+    return _kw.load_weights(keras_variable_map(encoder), weights, encoder.net_name)

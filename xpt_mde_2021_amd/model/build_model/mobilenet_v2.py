@@ -23,16 +23,17 @@ lands on exactly one tensor (tests/golden/mobilenet_v2_manifest.json).  Bug-comp
 (x / 127.5 - 1) is applied to images already in [-1, 1] (pretrained_nets.py:40); BatchNorm runs on its moving statistics
 (train_val.py:82) with trainable gamma / beta.  Unlike NASNet the stem convolution is SAME-padded, so nothing is resized.
 """
-import torch
+import functools
+
 import torch.nn as nn
 import torch.nn.functional as F
 
 from ...hip import conv as _conv
 from ...hip import ops as _ops
-from ...hip.lib import half as _half
 from ...utils.util_class import WrongInputException
-from .pretrained_nets import (BN_EPS, FrozenBatchNorm, _from_keras, _to_keras, conv1x1_bn, correct_pad, read_keras_weight_file,
-                              zero_pad)
+from . import keras_weights as _kw
+from .keras_weights import _from_keras  # noqa: F401  (the layout converter stays addressable through this module)
+from .pretrained_nets import BN_EPS, FrozenBatchNorm, KerasApplicationEncoder, conv1x1_bn, correct_pad, zero_pad
 
 # (output channels, stride) of block_1 .. block_16, expansion 6 (keras mobilenet_v2.py, alpha = 1.0)
 BLOCKS = ((24, 2), (24, 1), (32, 2), (32, 1), (32, 1), (64, 2), (64, 1), (64, 1), (64, 1), (96, 1), (96, 1), (96, 1),
@@ -40,9 +41,7 @@ BLOCKS = ((24, 2), (24, 1), (32, 2), (32, 1), (32, 1), (64, 2), (64, 1), (64, 1)
 TAP_BLOCKS = (1, 3, 6, 13)                 # block_<k>_expand_relu; the fifth tap is out_relu
 
 
-def _he(conv):
-    nn.init.kaiming_normal_(conv.weight, mode="fan_in", nonlinearity="relu")
-    return conv
+_he = KerasApplicationEncoder.he
 
 
 class InvertedResidual(nn.Module):
@@ -70,13 +69,14 @@ class InvertedResidual(nn.Module):
         return conv1x1_bn(d, self.project.weight, self.project_bn, residual=x if self.use_res else None), h
 
 
-class MobileNetV2Encoder(nn.Module):
+class MobileNetV2Encoder(KerasApplicationEncoder):
     """Keras MobileNetV2(alpha=1.0, include_top=False) with the five taps of scaled_layers.json.
 
     forward(image NCHW in [-1,1], H and W multiples of 32) -> [c1 (1/2, 96 ch), c2 (1/4, 144), c3 (1/8, 192), c4 (1/16, 576),
     c5 (1/32, 1280)], all post-ReLU6."""
     TAP_NAMES = ("block_1_expand_relu", "block_3_expand_relu", "block_6_expand_relu", "block_13_expand_relu", "out_relu")
     TAP_CHANNELS = (96, 144, 192, 576, 1280)
+    net_name = "MobileNetV2"
 
     def __init__(self):
         super().__init__()
@@ -92,10 +92,6 @@ class MobileNetV2Encoder(nn.Module):
         self.bn_last = FrozenBatchNorm(1280)                        # Conv_1_bn
         self.out_channels = 1280
 
-    def tap_layout(self):
-        """[(physical channels, logical index set or None)] of the five taps: no structurally-zero channels here."""
-        return [(c, None) for c in self.TAP_CHANNELS]
-
     def preprocess(self, image):
         """pretrained_nets.py:36-43 without the resize (the stem convolution is SAME-padded)."""
         return image / 127.5 - 1.0
@@ -103,17 +99,14 @@ class MobileNetV2Encoder(nn.Module):
     def stem(self, image):
         """Conv1 + bn_Conv1, pre-activation (its ReLU6 rides in expanded_conv's depthwise loads)."""
         x = self.preprocess(image)
-        if _conv.usable(x, self.conv1, 1.0):                          # the matrix-core convolution: 3 -> 8 channels, 16-byte pixels
-            x = F.pad(x.to(_half()), (0, 0, 0, 0, 0, 5)).contiguous(memory_format=torch.channels_last)
-            x = _conv.conv2d_same(x, self.conv1.weight, None, 2, 1.0)
+        if _conv.usable(x, self.conv1, 1.0):
+            x = self.stem_matrix_core(x, self.conv1, 2)
         else:                                                         # host tensors / fp32: ZeroPadding2D(correct_pad) + valid
             x = F.conv2d(zero_pad(x, correct_pad(x.shape[2], x.shape[3], 3)), self.conv1.weight, None, 2)
         return self.bn_conv1(x)
 
     def forward(self, image, physical_taps=False):
-        h, w = image.shape[2:]
-        if h % 32 or w % 32:
-            raise WrongInputException(f"MobileNetV2 encoder: image {h} x {w} is not a multiple of 32 in both extents")
+        self.check_image(image)
         x = self.stem(image)
         taps = []
         for k, block in enumerate(self.blocks):                       # k = 0: expanded_conv, k >= 1: block_k
@@ -128,14 +121,9 @@ class MobileNetV2Encoder(nn.Module):
 # ------------------------------------------------------------------------------------------ Keras weights
 def keras_variable_map(encoder):
     """{keras variable name: (tensor of the encoder, kind)} with kind in {"conv", "depthwise", "vector"}
-    (tf.keras.applications.MobileNetV2 layer names; layouts as pretrained_nets._to_keras)."""
+    (tf.keras.applications.MobileNetV2 layer names; layouts as keras_weights._to_keras)."""
     out = {}
-
-    def bn(name, module):
-        out[f"{name}/gamma"] = (module.weight, "vector")
-        out[f"{name}/beta"] = (module.bias, "vector")
-        out[f"{name}/moving_mean"] = (module.running_mean, "vector")
-        out[f"{name}/moving_variance"] = (module.running_var, "vector")
+    bn = functools.partial(_kw.bn, out)
 
     out["Conv1/kernel"] = (encoder.conv1.weight, "conv")
     bn("bn_Conv1", encoder.bn_conv1)
@@ -157,28 +145,10 @@ def keras_variable_map(encoder):
 
 def export_keras_weights(encoder):
     """{keras variable name: float32 array in the keras layout} of the encoder's current weights."""
-    return {name: _to_keras(kind, t.detach()).contiguous().float().cpu() for name, (t, kind) in keras_variable_map(encoder).items()}
+    return _kw.export_weights(keras_variable_map(encoder))
 
 
 def load_keras_weights(encoder, weights):
     """Fills the encoder from Keras MobileNetV2(include_top=False) variables (a path or a {name: array} dict).  Strict: a
     missing, unknown or mis-shaped variable raises; nothing is loaded partially."""
-    if not isinstance(weights, dict):
-        weights = read_keras_weight_file(weights)
-    table = keras_variable_map(encoder)
-    missing = sorted(set(table) - set(weights))
-    unknown = sorted(set(weights) - set(table))
-    if missing or unknown:
-        raise WrongInputException(f"MobileNetV2 weights: {len(missing)} variables missing (e.g. {missing[:3]}), "
-                                  f"{len(unknown)} not part of the no-top model (e.g. {unknown[:3]})")
-    staged = {}
-    for name, (t, kind) in table.items():
-        a = torch.as_tensor(weights[name])
-        want = tuple(_to_keras(kind, t).shape)
-        if tuple(a.shape) != want:
-            raise WrongInputException(f"{name}: file has shape {tuple(a.shape)}, the model expects {want}")
-        staged[name] = _from_keras(kind, a)
-    with torch.no_grad():
-        for name, (t, kind) in table.items():
-            t.copy_(staged[name].to(device=t.device, dtype=t.dtype))
-    return len(staged)
+    return _kw.load_weights(keras_variable_map(encoder), weights, "MobileNetV2")

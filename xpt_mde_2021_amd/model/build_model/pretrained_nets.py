@@ -19,6 +19,9 @@ Bug-compatible details kept (SURVEY 7 "Hard parts" h, i):
   * the model is called without training=True (train_val.py:82), so every BatchNormalization uses its moving
     statistics (never updated) while gamma / beta are trained: FrozenBatchNorm below.
 """
+import functools
+import importlib
+
 import torch
 import torch.nn as nn
 from ...hip.lib import half as _half      # torch dtype of the 16-bit activations (bf16 | fp16 build of the library)
@@ -29,6 +32,8 @@ from ...hip import ops as _ops
 from ...utils.util_class import WrongInputException
 from ...hip import conv as _conv
 from ..model_util.layer_ops import conv2d_library, same_pad
+from . import keras_weights as _kw
+from .keras_weights import _from_keras, _store_logical, _to_keras, logical_view, read_keras_weight_file  # noqa: F401  (re-exported)
 
 _FUSED_STEM_RELU = __import__("os").environ.get("XPT_DEBUG_STEM_RELU", "1") == "1"         # A/B: the stem's ReLU inside its BatchNorm launch
 _LIBRARY_WGRAD = __import__("os").environ.get("XPT_DEBUG_LIBRARY_WGRAD", "0") == "1"     # A/B switch: rocBLAS weight gradient
@@ -1297,6 +1302,33 @@ class NASNetMobileEncoder(nn.Module):
         return [taps.found[k] for k in self.TAP_ACTIVATIONS]
 
 
+class KerasApplicationEncoder(nn.Module):
+    """What the MobileNetV2 / EfficientNet / ResNet50V2 encoders share.  A subclass sets `net_name` and TAP_CHANNELS."""
+
+    @staticmethod
+    def he(conv):
+        nn.init.kaiming_normal_(conv.weight, mode="fan_in", nonlinearity="relu")
+        if conv.bias is not None:
+            nn.init.zeros_(conv.bias)
+        return conv
+
+    def tap_layout(self):
+        """[(physical channels, logical index set or None)] of the five taps: no structurally-zero channels here."""
+        return [(c, None) for c in self.TAP_CHANNELS]
+
+    def check_image(self, image):
+        h, w = image.shape[2:]
+        if h % 32 or w % 32:
+            raise WrongInputException(f"{self.net_name} encoder: image {h} x {w} is not a multiple of 32 in both extents")
+
+    @staticmethod
+    def stem_matrix_core(x, conv, stride, pad=None):
+        """The stem on the matrix-core convolution: 3 -> 8 channels (16-byte pixels), channels_last; pad=None is TF SAME, an
+        int that many zeros on every side (read as out-of-range taps) and then valid."""
+        x = F.pad(x.to(_half()), (0, 0, 0, 0, 0, 5)).contiguous(memory_format=torch.channels_last)
+        return _conv.conv2d_same(x, conv.weight, conv.bias, stride, 1.0, pad=pad)
+
+
 # ------------------------------------------------------------------------------------------ Keras weights
 # tf.keras.applications.NASNetMobile addresses its variables by LAYER NAME / VARIABLE NAME (stem_conv1/kernel,
 # separable_conv_1_normal_left1_0/depthwise_kernel, separable_conv_1_bn_normal_left1_0/moving_mean, ...).  The map below
@@ -1306,35 +1338,10 @@ class NASNetMobileEncoder(nn.Module):
 CELL_BLOCK_IDS = ("stem_1", "stem_2", "0", "1", "2", "3", "reduce_4", "5", "6", "7", "8", "reduce_8", "9", "10", "11", "12")
 
 
-def _to_keras(kind, t):
-    """torch layout -> keras layout: conv OIHW -> HWIO, depthwise [C,1,k,k] -> [k,k,C,1]."""
-    if kind == "conv":
-        return t.permute(2, 3, 1, 0)
-    if kind == "depthwise":
-        return t.permute(2, 3, 0, 1)
-    return t
-
-
-def _from_keras(kind, a):
-    if kind == "conv":
-        return a.permute(3, 2, 0, 1)
-    if kind == "depthwise":
-        return a.permute(2, 3, 0, 1)
-    return a
-
-
 def keras_variable_map(encoder):
     """{keras variable name: (tensor of the encoder, kind)} with kind in {"conv", "depthwise", "vector"}."""
     out = {}
-
-    def conv(name, module):
-        out[f"{name}/kernel"] = (module.weight, "conv")
-
-    def bn(name, module):
-        out[f"{name}/gamma"] = (module.weight, "vector")
-        out[f"{name}/beta"] = (module.bias, "vector")
-        out[f"{name}/moving_mean"] = (module.running_mean, "vector")
-        out[f"{name}/moving_variance"] = (module.running_var, "vector")
+    conv, bn = functools.partial(_kw.conv, out), functools.partial(_kw.bn, out)
 
     def sep_block(block_id, block):
         for k, (sep, norm) in enumerate(((block.conv1, block.bn1), (block.conv2, block.bn2)), start=1):
@@ -1374,99 +1381,27 @@ def logical_entries(encoder):
     return {id(t): (o, i) for t, o, i in encoder.structural_pads()}
 
 
-def logical_view(t, sel):
-    """The logical entries of t (a copy when t carries structural zeros, t itself otherwise)."""
-    if sel is None:
-        return t
-    o, i = sel
-    if o is not None:
-        t = t.index_select(0, o.to(t.device))
-    if i is not None:
-        t = t.index_select(1, i.to(t.device))
-    return t
-
-
-def _store_logical(t, sel, value, fill=0.0):
-    if sel is None:
-        t.copy_(value.to(device=t.device, dtype=t.dtype))
-        return
-    o, i = sel
-    full = torch.full_like(t, fill)
-    oo = (o if o is not None else torch.arange(t.shape[0])).to(t.device)
-    v = value.to(device=t.device, dtype=t.dtype)
-    if i is not None:
-        full[oo[:, None], i.to(t.device)[None, :]] = v
-    else:
-        full[oo] = v
-    t.copy_(full)
-
-
 def export_keras_weights(encoder):
     """{keras variable name: float32 array in the keras layout} of the encoder's current weights."""
-    sel = logical_entries(encoder)
-    return {name: _to_keras(kind, logical_view(t.detach(), sel.get(id(t)))).contiguous().float().cpu()
-            for name, (t, kind) in keras_variable_map(encoder).items()}
-
-
-def read_keras_weight_file(path):
-    """{variable name: numpy array} from an .npz keyed by keras variable names (INTEGRATION.md has the one-line export to
-    run where Keras is installed) or from Keras' own NASNet-mobile-no-top.h5 when h5py is importable."""
-    import numpy as np
-    if str(path).endswith(".npz"):
-        with np.load(path) as z:
-            return {k[:-2] if k.endswith(":0") else k: z[k] for k in z.files}
-    if str(path).endswith((".h5", ".hdf5")):
-        try:
-            import h5py
-        except ImportError as e:
-            raise WrongInputException("reading a Keras .h5 file needs h5py (not installed): convert it to .npz, "
-                                      "INTEGRATION.md") from e
-        out = {}
-        with h5py.File(path, "r") as f:
-            root = f["model_weights"] if "model_weights" in f else f
-
-            def visit(name, obj):
-                if isinstance(obj, h5py.Dataset):
-                    parts = name.split("/")
-                    var = parts[-1][:-2] if parts[-1].endswith(":0") else parts[-1]
-                    out[f"{parts[-2]}/{var}"] = obj[()]
-            root.visititems(visit)
-        return out
-    raise WrongInputException(f"unknown weight file type: {path}")
+    return _kw.export_weights(keras_variable_map(encoder), logical_entries(encoder))
 
 
 def load_keras_weights(encoder, weights):
     """Fills the encoder from Keras NASNetMobile(include_top=False) variables (a path or a {name: array} dict).  Strict: a
     missing, unknown or mis-shaped variable raises; nothing is loaded partially."""
-    if not isinstance(weights, dict):
-        weights = read_keras_weight_file(weights)
-    table = keras_variable_map(encoder)
-    missing = sorted(set(table) - set(weights))
-    unknown = sorted(set(weights) - set(table))
-    if missing or unknown:
-        raise WrongInputException(f"NASNet-Mobile weights: {len(missing)} variables missing (e.g. {missing[:3]}), "
-                                  f"{len(unknown)} not part of the no-top model (e.g. {unknown[:3]})")
-    staged = {}
-    sel = logical_entries(encoder)
-    for name, (t, kind) in table.items():
-        a = torch.as_tensor(weights[name])
-        want = tuple(_to_keras(kind, logical_view(t, sel.get(id(t)))).shape)
-        if tuple(a.shape) != want:
-            raise WrongInputException(f"{name}: file has shape {tuple(a.shape)}, the model expects {want}")
-        staged[name] = _from_keras(kind, a)
-    with torch.no_grad():
-        for name, (t, kind) in table.items():
-            _store_logical(t, sel.get(id(t)), staged[name], fill=1.0 if name.endswith("/moving_variance") else 0.0)
-    return len(staged)
+    return _kw.load_weights(keras_variable_map(encoder), weights, "NASNet-Mobile", logical_entries(encoder))
 
 
 class PretrainedModel:
     """pretrained_nets.py:11-117 interface: PretrainedModel(net_name, use_pt_weight).encoder() builds the module
     whose forward is the reference's `.encode(input_image)`."""
-    # (MobileNetV2: build_model/mobilenet_v2.py; EfficientNetB0 / B3 / B5 / B7: build_model/efficientnet.py; ResNet50V2:
-    #  build_model/resnet_v2.py)
     SUPPORTED = ("NASNetMobile", "MobileNetV2", "EfficientNetB0", "EfficientNetB3", "EfficientNetB5", "EfficientNetB7",
                  "ResNet50V2")
+    # net name -> (module of build_model/, constructor(module, net name))
+    ENCODERS = {"NASNetMobile": ("pretrained_nets", lambda m, name: m.NASNetMobileEncoder()),
+                "MobileNetV2": ("mobilenet_v2", lambda m, name: m.MobileNetV2Encoder()),
+                "ResNet50V2": ("resnet_v2", lambda m, name: m.ResNet50V2Encoder()),
+                **{name: ("efficientnet", lambda m, name: m.EfficientNetEncoder(name)) for name in SUPPORTED[2:6]}}
     WEIGHT_ENV = {"NASNetMobile": "XPT_NASNET_WEIGHTS", "MobileNetV2": "XPT_MOBILENETV2_WEIGHTS",
                   "EfficientNetB0": "XPT_EFFICIENTNETB0_WEIGHTS", "EfficientNetB3": "XPT_EFFICIENTNETB3_WEIGHTS",
                   "EfficientNetB5": "XPT_EFFICIENTNETB5_WEIGHTS", "EfficientNetB7": "XPT_EFFICIENTNETB7_WEIGHTS",
@@ -1489,25 +1424,9 @@ class PretrainedModel:
         self.net_name = net_name
 
     def encoder(self):
-        if self.net_name == "MobileNetV2":
-            from . import mobilenet_v2 as mv2          # (imports this module)
-            net = mv2.MobileNetV2Encoder()
-            if self.weight_file:
-                mv2.load_keras_weights(net, self.weight_file)
-            return net
-        if self.net_name.startswith("EfficientNet"):
-            from . import efficientnet as eff          # (imports this module)
-            net = eff.EfficientNetEncoder(self.net_name)
-            if self.weight_file:
-                eff.load_keras_weights(net, self.weight_file)
-            return net
-        if self.net_name == "ResNet50V2":
-            from . import resnet_v2 as rn2             # (imports this module)
-            net = rn2.ResNet50V2Encoder()
-            if self.weight_file:
-                rn2.load_keras_weights(net, self.weight_file)
-            return net
-        net = NASNetMobileEncoder()
+        module, make = self.ENCODERS[self.net_name]
+        module = importlib.import_module(f".{module}", __package__)       # (lazy: the backbone modules import this one)
+        net = make(module, self.net_name)
         if self.weight_file:
-            load_keras_weights(net, self.weight_file)
+            module.load_keras_weights(net, self.weight_file)
         return net

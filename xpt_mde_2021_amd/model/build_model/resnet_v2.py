@@ -25,6 +25,8 @@ the no-top model lands on exactly one tensor (tests/golden/resnet50v2_manifest.j
   * pool1's padding is zeros that take part in the max (the conv1_conv output is signed);
   * BatchNorm runs on its moving statistics (train_val.py:82) with trainable gamma / beta; epsilon is 1.001e-5.
 """
+import functools
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -33,7 +35,9 @@ from ...hip import conv as _conv
 from ...hip import ops as _ops
 from ...hip.lib import half as _half
 from ...utils.util_class import WrongInputException
-from .pretrained_nets import FrozenBatchNorm, _from_keras, _to_keras, conv1x1, read_keras_weight_file
+from . import keras_weights as _kw
+from .keras_weights import _from_keras  # noqa: F401  (the layout converter stays addressable through this module)
+from .pretrained_nets import FrozenBatchNorm, KerasApplicationEncoder, conv1x1
 
 RES_BN_EPS = 1.001e-5                    # keras resnet_v2: BatchNormalization(epsilon=1.001e-5) everywhere
 STACKS = ((64, 3, 2), (128, 4, 2), (256, 6, 2), (512, 3, 1))          # (filters, blocks, stride1) of conv2 .. conv5
@@ -41,11 +45,7 @@ CAFFE_MEAN_BGR = (103.939, 116.779, 123.68)
 TAP_NAMES = ("conv1_conv", "conv2_block3_1_relu", "conv3_block4_1_relu", "conv4_block6_1_relu", "post_relu")
 
 
-def _he(conv):
-    nn.init.kaiming_normal_(conv.weight, mode="fan_in", nonlinearity="relu")
-    if conv.bias is not None:
-        nn.init.zeros_(conv.bias)
-    return conv
+_he = KerasApplicationEncoder.he
 
 
 class ResBatchNorm(FrozenBatchNorm):
@@ -88,13 +88,14 @@ class Block2(nn.Module):
         return out, nxt, h1
 
 
-class ResNet50V2Encoder(nn.Module):
+class ResNet50V2Encoder(KerasApplicationEncoder):
     """Keras ResNet50V2(include_top=False) with the five taps of scaled_layers.json.
 
     forward(image NCHW in [-1,1], H and W multiples of 32) -> [c1 (1/2, 64 ch, the LINEAR conv1_conv output), c2 (1/4, 64),
     c3 (1/8, 128), c4 (1/16, 256), c5 (1/32, 2048)]; c2 .. c5 post-ReLU."""
     TAP_NAMES = TAP_NAMES
     TAP_CHANNELS = (64, 64, 128, 256, 2048)
+    net_name = "ResNet50V2"
 
     def __init__(self):
         super().__init__()
@@ -113,10 +114,6 @@ class ResNet50V2Encoder(nn.Module):
         self.post_bn = ResBatchNorm(cin)
         self.out_channels = cin
 
-    def tap_layout(self):
-        """[(physical channels, logical index set or None)] of the five taps: no structurally-zero channels here."""
-        return [(c, None) for c in self.TAP_CHANNELS]
-
     def preprocess(self, image):
         """applications.resnet.preprocess_input (caffe mode) on the [-1, 1] image, as the reference applies it."""
         key = (image.device, image.dtype)
@@ -129,15 +126,11 @@ class ResNet50V2Encoder(nn.Module):
         x = self.preprocess(image)
         dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else x.dtype
         if x.is_cuda and dtype == _half() and self.conv1.weight.dtype == torch.float32:
-            # the matrix-core convolution: 3 -> 8 channels (16-byte pixels), the padding read as out-of-range taps
-            x = F.pad(x.to(_half()), (0, 0, 0, 0, 0, 5)).contiguous(memory_format=torch.channels_last)
-            return _conv.conv2d_same(x, self.conv1.weight, self.conv1.bias, 2, 1.0, pad=3)
+            return self.stem_matrix_core(x, self.conv1, 2, pad=3)
         return F.conv2d(F.pad(x, (3, 3, 3, 3)), self.conv1.weight, self.conv1.bias, 2)
 
     def forward(self, image, physical_taps=False):
-        h, w = image.shape[2:]
-        if h % 32 or w % 32:
-            raise WrongInputException(f"ResNet50V2 encoder: image {h} x {w} is not a multiple of 32 in both extents")
+        self.check_image(image)
         c1 = self.stem(image)
         taps = [c1]
         x = _ops.maxpool3s2_zero(c1)                                  # pool1_pad + pool1_pool
@@ -154,19 +147,9 @@ class ResNet50V2Encoder(nn.Module):
 # ------------------------------------------------------------------------------------------ Keras weights
 def keras_variable_map(encoder):
     """{keras variable name: (tensor of the encoder, kind)} with kind in {"conv", "vector"}
-    (tf.keras.applications.resnet_v2 layer names; layouts as pretrained_nets._to_keras)."""
+    (tf.keras.applications.resnet_v2 layer names; layouts as keras_weights._to_keras)."""
     out = {}
-
-    def bn(name, module):
-        out[f"{name}/gamma"] = (module.weight, "vector")
-        out[f"{name}/beta"] = (module.bias, "vector")
-        out[f"{name}/moving_mean"] = (module.running_mean, "vector")
-        out[f"{name}/moving_variance"] = (module.running_var, "vector")
-
-    def conv(name, module):
-        out[f"{name}/kernel"] = (module.weight, "conv")
-        if module.bias is not None:
-            out[f"{name}/bias"] = (module.bias, "vector")
+    bn, conv = functools.partial(_kw.bn, out), functools.partial(_kw.conv, out)
 
     conv("conv1_conv", encoder.conv1)
     if len(encoder.blocks) != sum(n for _, n, _ in STACKS):
@@ -186,28 +169,10 @@ def keras_variable_map(encoder):
 
 def export_keras_weights(encoder):
     """{keras variable name: float32 array in the keras layout} of the encoder's current weights."""
-    return {name: _to_keras(kind, t.detach()).contiguous().float().cpu() for name, (t, kind) in keras_variable_map(encoder).items()}
+    return _kw.export_weights(keras_variable_map(encoder))
 
 
 def load_keras_weights(encoder, weights):
     """Fills the encoder from Keras ResNet50V2(include_top=False) variables (a path or a {name: array} dict).  Strict: a
     missing, unknown or mis-shaped variable raises; nothing is loaded partially."""
-    if not isinstance(weights, dict):
-        weights = read_keras_weight_file(weights)
-    table = keras_variable_map(encoder)
-    missing = sorted(set(table) - set(weights))
-    unknown = sorted(set(weights) - set(table))
-    if missing or unknown:
-        raise WrongInputException(f"ResNet50V2 weights: {len(missing)} variables missing (e.g. {missing[:3]}), "
-                                  f"{len(unknown)} not part of the no-top model (e.g. {unknown[:3]})")
-    staged = {}
-    for name, (t, kind) in table.items():
-        a = torch.as_tensor(weights[name])
-        want = tuple(_to_keras(kind, t).shape)
-        if tuple(a.shape) != want:
-            raise WrongInputException(f"{name}: file has shape {tuple(a.shape)}, the model expects {want}")
-        staged[name] = _from_keras(kind, a)
-    with torch.no_grad():
-        for name, (t, kind) in table.items():
-            t.copy_(staged[name].to(device=t.device, dtype=t.dtype))
-    return len(staged)
+    return _kw.load_weights(keras_variable_map(encoder), weights, "ResNet50V2")
