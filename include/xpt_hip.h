@@ -423,6 +423,19 @@ int xpt_conv2d_bwd_weight_partials(const void* g, const void* x, float* partials
                                    int PW, int C, int Cr, long long xpitch, int N, long long gpitch, int KH, int KW,
                                    int stride, int pad_t, int pad_l, int OH, int OW, int upsample, void* stream);
 int xpt_restack_bf16(const float* image5d, void* out, int B, int S, int H, int W, int Cp, void* stream);
+/* UpSampling2D(2, interpolation="bilinear") of upsample_2x_d (model/build_model/depth_net.py:71-74, DEPTH_UPSAMPLE_INTERP =
+ * "bilinear") as a third operand-load mode, upsample = 2, of xpt_conv2d_fwd and xpt_conv2d_bwd_weight_partials (3 x 3,
+ * stride 1, pad 1, OH x OW = 2PH x 2PW): a tap reads 0.75 / 0.25 of its two nearest physical pixels per axis (half-pixel
+ * centres, edge clamp), evaluated in fp32 and rounded once to the 16-bit format; taps outside the up-sampled map are zeros.
+ * xpt_conv2d_fwd_splitk / xpt_conv2d_fwd_stream do not serve the mode (XPT_ERR_ARG).
+ * xpt_conv2d_bwd_weight_splits_mode: the splits of xpt_conv2d_bwd_weight_partials under a given upsample mode (mode 2 runs the
+ *   general kernel's plan; 0 / 1: xpt_conv2d_bwd_weight_splits).
+ * xpt_bilinear2x_adjoint: the data gradient's last step: gu [B,2IH,2IW,C] (gradient w.r.t. the up-sampled map, from
+ *   xpt_conv2d_bwd_data with fold2x2 = 0) -> dx [B,IH,IW,C], the transposed stencil with the clamped taps' weights on the
+ *   border pixels; C % 8 == 0, pixel pitches in elements. */
+int xpt_conv2d_bwd_weight_splits_mode(int B, int C, int N, int KH, int KW, int stride, int OH, int OW, int upsample);
+int xpt_bilinear2x_adjoint(const void* gu, long long gpitch, void* dx, long long dxpitch, int B, int IH, int IW, int C,
+                           void* stream);
 
 /* ------------------------------------------------------------------ a2: decoder prediction heads
  * replaces the Conv2D(1, 3, padding="same", activation linear) of get_scaled_depth (model/build_model/depth_net.py:87-92)
@@ -453,6 +466,12 @@ int xpt_depth_head_ms_fwd(int nscales, const float* const* x, float* const* dept
                           void* stream);
 int xpt_depth_head_ms_bwd(int nscales, const float* const* x, const float* const* g_depth, const float* const* g_disp,
                           float* const* gx, const long long* n, void* stream);
+/* ExponentialActivation (model/build_model/model_factory.py:111-115) with the same contract:
+ *   depth = exp(10 sigmoid(x + 1) - 5), disp = safe_rcp(depth). */
+int xpt_depth_head_exp_ms_fwd(int nscales, const float* const* x, float* const* depth, float* const* disp, const long long* n,
+                              void* stream);
+int xpt_depth_head_exp_ms_bwd(int nscales, const float* const* x, const float* const* g_depth, const float* const* g_disp,
+                              float* const* gx, const long long* n, void* stream);
 
 /* tf.keras.layers.GlobalAveragePooling2D closing PoseNet (model/build_model/pose_net.py:45) on an NHWC map x [B,HW,C]
  * (dtype 0 float32 / 1 bfloat16) -> y float32 [B,C]; bwd: g float32 [B,C] -> dx [B,HW,C] of that dtype = g / HW. */

@@ -2,6 +2,11 @@
 (forward / data gradient / weight-gradient partials) next to MIOpen's forward / backward for the same shape.
 
     python tools/bench_conv.py [batch] [plan ...]      plan = xpt_conv2d_tune code (RM*100 + RN*10 + log2 NKW), 0 = auto
+    python tools/bench_conv.py [batch] --upsample {nearest,bilinear}
+        the five conv1 layers of the decoder (up4a .. up0a) alone, through the product's dispatcher (hip/conv.py): forward,
+        forward + backward w.r.t. the input (activation backward + data gradient [+ adjoint]) and the weight-gradient partials,
+        each as a replayed graph of 20 calls; with "bilinear" also the framework route (16-bit F.interpolate + the same convolution
+        on the materialised tensor, what XPT_DEBUG_ATEN_BILINEAR=1 runs) next to the fused operand-load mode.
 """
 import math
 import os
@@ -13,6 +18,13 @@ import torch.nn.functional as F  # noqa: E402
 
 from xpt_mde_2021_amd.hip import conv as xc, lib as _lib  # noqa: E402
 
+UPSAMPLE = None
+if "--upsample" in sys.argv:
+    at = sys.argv.index("--upsample")
+    UPSAMPLE = sys.argv[at + 1]
+    if UPSAMPLE not in ("nearest", "bilinear"):
+        raise SystemExit("--upsample nearest | bilinear")
+    del sys.argv[at:at + 2]
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 8
 plans = [int(a) for a in sys.argv[2:]] or [0]
 lib = _lib.load()
@@ -46,6 +58,55 @@ def timeit(fn, n=20):
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) * 1e3 / n
 
+
+def bench_upsample(mode):
+    half = _lib.half()
+    st = lambda: torch.cuda.current_stream().cuda_stream      # noqa: E731
+    routes = ["fused"] + (["framework"] if mode == "bilinear" else [])
+    print(f"batch {B}; conv1 layers read through the {mode} 2x up-sampling; us per call: forward / backward w.r.t. x (forward + "
+          f"backward in one graph, minus the forward) / weight-gradient partials / sum, per route {routes}")
+    totals = {r: 0.0 for r in routes}
+    for name, cin, cout, k, s, H, W, ups in LAYERS:
+        if not ups:
+            continue
+        cp = xc.round_up(cin, 8)
+        x = torch.randn(B, cp, H, W, device="cuda").to(half).contiguous(memory_format=torch.channels_last).requires_grad_(True)
+        w = (torch.randn(cout, cin, 3, 3, device="cuda") / math.sqrt(cin * 9)).contiguous(memory_format=torch.channels_last)
+        bias = torch.zeros(cout, device="cuda")
+        gy = torch.randn(B, cout, 2 * H, 2 * W, device="cuda").to(half).contiguous(memory_format=torch.channels_last)
+        cells = []
+        for route in routes:
+            def forward():
+                if route == "framework":
+                    return xc.conv2d_same(F.interpolate(x, scale_factor=2, mode="bilinear", align_corners=False), w, bias, 1, 0.1)
+                return xc.conv2d_same(x, w, bias, 1, 0.1, upsample=mode)
+
+            def fwd_only():
+                with torch.no_grad():
+                    forward()
+
+            forward()                                      # (eager: packs the weight's operand layouts before any capture)
+            t_f = timeit(fwd_only)
+            # forward and backward inside ONE capture: the autograd engine runs a node on the stream of its forward, and a
+            # backward whose forward ran outside the capture would launch on the default stream while another one captures
+            t_b = timeit(lambda: torch.autograd.grad(forward(), x, gy)) - t_f
+            up_mode = 0 if route == "framework" else xc.upsample_mode(mode)
+            xin = F.interpolate(x.detach(), scale_factor=2, mode="bilinear", align_corners=False) if route == "framework" else x.detach()
+            PH, PW = xin.shape[2:]
+            nsplit = lib.xpt_conv2d_bwd_weight_splits_mode(B, cp, cout, 3, 3, 1, 2 * H, 2 * W, up_mode)
+            part = torch.empty(nsplit * cout * 9 * cin, dtype=torch.float32, device="cuda")
+            t_w = timeit(lambda: _lib.check(lib.xpt_conv2d_bwd_weight_partials(
+                gy.data_ptr(), xin.data_ptr(), part.data_ptr(), part.numel(), B, PH, PW, cp, cin, cp, cout, cout, 3, 3, 1, 1, 1,
+                2 * H, 2 * W, up_mode, st()), "wgrad"))
+            totals[route] += t_f + t_b + t_w
+            cells.append(f"{route} {t_f:6.1f} {t_b:6.1f} {t_w:6.1f} = {t_f + t_b + t_w:6.1f}")
+        print(f"{name:6s} {cin:4d}->{cout:3d} {2 * H:3d}x{2 * W:3d} | " + " | ".join(cells), flush=True)
+    print("totals us:", {k_: round(v, 1) for k_, v in totals.items()})
+
+
+if UPSAMPLE is not None:
+    bench_upsample(UPSAMPLE)
+    sys.exit(0)
 
 tot = {}
 print(f"batch {B}; us per call: fwd / dgrad / wgrad(partials) per plan {plans}; MIOpen bf16 fwd / bwd(dx+dw)")

@@ -639,6 +639,208 @@ __global__ __launch_bounds__(256) void conv_halo_kernel(ConvArgs a, HaloPlan hp)
   }
 }
 
+// ------------------------------------------------------------------------------------------------ halo tiles, bilinear-2x input
+// UpSampling2D(2, "bilinear") of upsample_2x_d (model/build_model/depth_net.py:71-74) as an operand-load mode of the halo-tile
+// kernel, for the 3 x 3 stride-1 SAME layers that read through it (conv1 of every decoder level).  The staged halo is the
+// LOGICAL (up-sampled) 10 x 18 window of the tile: every staged vector is interpolated in fp32 from its four physical
+// neighbours (half-pixel centres, edge clamp: the taps and weights of at::upsample_bilinear2d(align_corners=False)) and rounded
+// ONCE to the 16-bit format -- the rounding the materialised tensor would have had --; logical pixels outside the up-sampled
+// map are the convolution's zero padding.  Behind the staging it is conv_halo_kernel<1, true> for a direct input (a.shift = 0,
+// a.Hlim x a.Wlim = 2 PH x 2 PW, a.sgn = 1, no quad fold); a kernel of its own so that the code of the one above does not change.
+__device__ __forceinline__ void bil_taps(int y, int n, int& i0, int& i1, float& l) {
+  const float src = fmaxf(0.5f * (float)y - 0.25f, 0.f);
+  i0 = (int)src;
+  i1 = i0 + 1 < n ? i0 + 1 : n - 1;
+  l = src - (float)i0;
+}
+
+// (1 - lh) ((1 - lw) a00 + lw a01) + lh ((1 - lw) a10 + lw a11) on 8 packed 16-bit channels
+__device__ __forceinline__ uint4 bil_lerp8(const uint4& a00, const uint4& a01, const uint4& a10, const uint4& a11, float lh,
+                                           float lw) {
+  const unsigned p00[4] = {a00.x, a00.y, a00.z, a00.w}, p01[4] = {a01.x, a01.y, a01.z, a01.w};
+  const unsigned p10[4] = {a10.x, a10.y, a10.z, a10.w}, p11[4] = {a11.x, a11.y, a11.z, a11.w};
+  const float mh = 1.f - lh, mw = 1.f - lw;
+  unsigned o[4];
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float lo = mh * (mw * xpt_h2f_lo(p00[k]) + lw * xpt_h2f_lo(p01[k])) + lh * (mw * xpt_h2f_lo(p10[k]) + lw * xpt_h2f_lo(p11[k]));
+    const float hi = mh * (mw * xpt_h2f_hi(p00[k]) + lw * xpt_h2f_hi(p01[k])) + lh * (mw * xpt_h2f_hi(p10[k]) + lw * xpt_h2f_hi(p11[k]));
+    o[k] = (unsigned)xpt_f2h(lo) | ((unsigned)xpt_f2h(hi) << 16);
+  }
+  return make_uint4(o[0], o[1], o[2], o[3]);
+}
+
+__global__ __launch_bounds__(256) void conv_halo_bilinear_kernel(ConvArgs a, HaloPlan hp) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char hl[];
+  const int XBYTES = hp.HR * hp.WR * hp.XP;
+  unsigned char* const lX = hl;
+  unsigned char* const lW = hl + XBYTES;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int r = lane & 31, h = lane >> 5;
+  constexpr int T = 9;
+
+  unsigned bx = blockIdx.x, by = blockIdx.y;
+  xpt_xcd_remap(a.xcd != 0, bx, by, gridDim.x, gridDim.y);
+  int tile = (int)by;
+  const int txi = tile % hp.tiles_x; tile /= hp.tiles_x;
+  const int tyi = tile % hp.tiles_y;
+  const int b = tile / hp.tiles_y;
+  const int oh0 = tyi * 8, ow0 = txi * 16;
+  const int n0 = bx * 32;
+  const int lo_h = oh0 + a.off_h, lo_w = ow0 + a.off_w;            // first logical row / column of the halo
+  const int WR = hp.WR, HPIX = hp.HR * WR;
+
+  // this lane's output pixel: wave w owns rows 2w, 2w + 1 of the tile
+  const int ty = 2 * wave + (r >> 4), tx = r & 15;
+  const int oh = oh0 + ty, ow = ow0 + tx;
+  const bool pok = oh < a.OH && ow < a.OW;
+  const int prow0 = pok ? ty : 0, pcol0 = pok ? tx : 0;            // halo position of the lane's tap (0, 0)
+
+  f32x16 acc;
+#pragma unroll
+  for (int q = 0; q < 16; ++q) acc[q] = 0.f;
+
+  const int CC = hp.CC, cv8 = CC >> 3, lc = cv8 == 8 ? 3 : (cv8 == 4 ? 2 : 1);
+  const int nrows = a.N - n0 < 32 ? a.N - n0 : 32;
+  const int xvecs = HPIX * cv8, wvecs = nrows * T * cv8;
+  const float inv_wr = 1.f / (float)WR, inv_t = 1.f / (float)T;
+  auto stage = [&](int c0) {
+    // the interpolated halo: 2 vectors = 8 loads in flight per thread
+    for (int v0 = tid; v0 < xvecs; v0 += 256 * 2) {
+      uint4 val[2];
+      int lo[2];
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int v = v0 + 256 * i;
+        const int cv = v & (cv8 - 1), rest = v >> lc;
+        const int c = c0 + cv * 8;
+        const int q = (int)(((float)rest + 0.5f) * inv_wr), rem = rest - q * WR;
+        const int lh = lo_h + q, lw = lo_w + rem;                // logical (up-sampled) pixel
+        const bool ok = v < xvecs && c < a.C && lh >= 0 && lh < a.Hlim && lw >= 0 && lw < a.Wlim;
+        int r0, r1, q0, q1;
+        float fh, fw;
+        bil_taps(ok ? lh : 0, a.PH, r0, r1, fh);
+        bil_taps(ok ? lw : 0, a.PW, q0, q1, fw);
+        const long long img = (long long)b * a.PH, cc = ok ? c : 0;
+        const uint4 a00 = *(const uint4*)(a.x + ((img + r0) * a.PW + q0) * a.xpitch + cc);
+        const uint4 a01 = *(const uint4*)(a.x + ((img + r0) * a.PW + q1) * a.xpitch + cc);
+        const uint4 a10 = *(const uint4*)(a.x + ((img + r1) * a.PW + q0) * a.xpitch + cc);
+        const uint4 a11 = *(const uint4*)(a.x + ((img + r1) * a.PW + q1) * a.xpitch + cc);
+        const uint4 ld = bil_lerp8(a00, a01, a10, a11, fh, fw);
+        const unsigned keep = ok ? 0xffffffffu : 0u;
+        val[i] = make_uint4(ld.x & keep, ld.y & keep, ld.z & keep, ld.w & keep);
+        lo[i] = v >= xvecs ? -1 : rest * hp.XP + cv * 16;
+      }
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+        if (lo[i] >= 0) *(uint4*)(hl + lo[i]) = val[i];
+    }
+    // the weight slab [row][tap][CC] (rows past N are neither staged nor stored)
+    for (int v = tid; v < wvecs; v += 256) {
+      const int cv = v & (cv8 - 1), rest = v >> lc;
+      const int c = c0 + cv * 8;
+      const int q = (int)(((float)rest + 0.5f) * inv_t), rem = rest - q * T;
+      const bool ok = c < a.C;
+      const uint4 ld = *(const uint4*)(a.w + (ok ? ((long long)(n0 + q) * T + rem) * a.C + c : 0));
+      const unsigned keep = ok ? 0xffffffffu : 0u;
+      *(uint4*)(lW + q * hp.WP + (rem * CC + cv * 8) * 2) = make_uint4(ld.x & keep, ld.y & keep, ld.z & keep, ld.w & keep);
+    }
+  };
+
+  const int nchunks = (a.C + CC - 1) / CC;
+  for (int ck = 0; ck < nchunks; ++ck) {
+    if (ck > 0) __syncthreads();                     // the previous chunk's operand reads are done
+    stage(ck * CC);
+    __syncthreads();
+    const int c_left = a.C - ck * CC;
+    const int k16n = c_left >= CC ? CC >> 4 : (c_left + 15) >> 4;      // uniform: 16-channel steps of this chunk that hold data
+    const unsigned char* const wA = lW + (r >= nrows ? 0 : r) * hp.WP + h * 16;      // (rows past N: any staged row will do)
+#pragma unroll
+    for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+      for (int kw = 0; kw < 3; ++kw) {
+        const unsigned char* const xB = lX + ((prow0 + kh) * WR + pcol0 + kw) * hp.XP + h * 16;
+        const unsigned char* const wT = wA + (kh * 3 + kw) * CC * 2;
+        for (int k16 = 0; k16 < k16n; ++k16) {
+          const uint4 fb = *(const uint4*)(xB + k16 * 32);
+          const uint4 fa = *(const uint4*)(wT + k16 * 32);
+          acc = XPT_MFMA_32X32X16(__builtin_bit_cast(bf16x8, fa), __builtin_bit_cast(bf16x8, fb), acc);
+        }
+      }
+  }
+
+  // ---- epilogue (that of the kernels above): register q = channel n0 + (q & 3) + 8 (q >> 2) + 4 h
+  const long long opix = ((long long)b * a.OH + oh) * a.OW + ow;
+  const bool vec_ok = (a.N % 4 == 0) && (a.ypitch % 4 == 0) && (((uintptr_t)a.y) % 8 == 0);
+#pragma unroll
+  for (int qg = 0; qg < 4; ++qg) {
+    float v[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) v[e] = acc[4 * qg + e];
+    const int n = n0 + 8 * qg + 4 * h;
+    if (!pok || n >= a.N) continue;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      if (a.bias != nullptr && n + e < a.N) v[e] += a.bias[n + e];
+      v[e] = v[e] > 0.f ? v[e] : v[e] * a.slope;
+    }
+    unsigned short* dst = a.y + opix * a.ypitch + n;
+    if (vec_ok) {
+      uint2 pk;
+      pk.x = (unsigned)f2bf(v[0]) | ((unsigned)f2bf(v[1]) << 16);
+      pk.y = (unsigned)f2bf(v[2]) | ((unsigned)f2bf(v[3]) << 16);
+      *(uint2*)dst = pk;
+    } else {
+#pragma unroll
+      for (int e = 0; e < 4; ++e)
+        if (n + e < a.N) dst[e] = f2bf(v[e]);
+    }
+  }
+}
+
+// Adjoint of the bilinear-2x operand load (the data gradient of a bilinear-mode convolution): gu [B,2 IH,2 IW,C] is the
+// gradient w.r.t. the up-sampled map (the mode-0 data gradient), dx [B,IH,IW,C] gathers it through the transposed stencil.
+// Per axis, input i was read by outputs 2i - 1 (0.25), 2i (0.75), 2i + 1 (0.75) and 2i + 2 (0.25); at the borders the
+// clamped tap falls onto the pixel itself, so out[0] and out[2n - 1] count 1.0 and the taps outside do not exist.
+// One thread per (pixel, 8 channels): 16 16-byte loads, fp32 sums, one rounding.
+__global__ __launch_bounds__(256) void bilinear2x_adjoint_kernel(const unsigned short* __restrict__ gu, long long gpitch,
+                                                                  unsigned short* __restrict__ dx, long long dxpitch, int IH,
+                                                                  int IW, int c8, long long total) {
+  const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= total) return;                                    // (total < 2^31: the launcher checks)
+  unsigned cv, j, i;
+  unsigned rest = xpt_divmod((unsigned)idx, (unsigned)c8, cv);
+  rest = xpt_divmod(rest, (unsigned)IW, j);
+  const unsigned b = xpt_divmod(rest, (unsigned)IH, i);
+  float acc[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) acc[e] = 0.f;
+  const float wts[4] = {0.25f, 0.75f, 0.75f, 0.25f};
+#pragma unroll
+  for (int dr = 0; dr < 4; ++dr) {
+    const int r = 2 * (int)i - 1 + dr;
+    if (r < 0 || r >= 2 * IH) continue;
+    const float wr = (r == 0 || r == 2 * IH - 1) ? 1.f : wts[dr];
+#pragma unroll
+    for (int dc = 0; dc < 4; ++dc) {
+      const int c = 2 * (int)j - 1 + dc;
+      if (c < 0 || c >= 2 * IW) continue;
+      const float w = wr * ((c == 0 || c == 2 * IW - 1) ? 1.f : wts[dc]);
+      const uint4 v = *(const uint4*)(gu + (((long long)b * 2 * IH + r) * 2 * IW + c) * gpitch + cv * 8);
+      acc[0] += w * xpt_h2f_lo(v.x); acc[1] += w * xpt_h2f_hi(v.x);
+      acc[2] += w * xpt_h2f_lo(v.y); acc[3] += w * xpt_h2f_hi(v.y);
+      acc[4] += w * xpt_h2f_lo(v.z); acc[5] += w * xpt_h2f_hi(v.z);
+      acc[6] += w * xpt_h2f_lo(v.w); acc[7] += w * xpt_h2f_hi(v.w);
+    }
+  }
+  uint4 o;
+  o.x = (unsigned)f2bf(acc[0]) | ((unsigned)f2bf(acc[1]) << 16);
+  o.y = (unsigned)f2bf(acc[2]) | ((unsigned)f2bf(acc[3]) << 16);
+  o.z = (unsigned)f2bf(acc[4]) | ((unsigned)f2bf(acc[5]) << 16);
+  o.w = (unsigned)f2bf(acc[6]) | ((unsigned)f2bf(acc[7]) << 16);
+  *(uint4*)(dx + (((long long)b * IH + i) * IW + j) * dxpitch + cv * 8) = o;
+}
+
 // ------------------------------------------------------------------------------------------------ weight packer
 // One launch per step converts every dense convolution weight from its fp32 master copy (any strides; the flat parameter
 // buffer keeps them in channels_last order [N][KH][KW][C]) into the two bf16 operand layouts of the kernels above:
@@ -791,6 +993,21 @@ int launch_halo(const ConvArgs& a, const HaloPlan& hp, size_t lds, hipStream_t s
   return xpt_launch_status();
 }
 
+// bilinear-2x input (3 x 3, stride 1): the halo-tile kernel in its interpolating mode is the one family that serves it
+int launch_halo_bilinear(const ConvArgs& a, hipStream_t s) {
+  HaloPlan hp;
+  size_t lds = 0;
+  if (!halo_plan(a, 1, hp, lds)) return XPT_ERR_SHAPE;
+  const long long gy = (long long)a.B * hp.tiles_y * hp.tiles_x;
+  if (gy > 65535) return XPT_ERR_SHAPE;
+  const dim3 grid((a.N + 31) / 32, (unsigned)gy);
+  ConvArgs b = a;
+  b.xcd = xpt_xcd_ok((unsigned long long)grid.x * grid.y);
+  XPT_BEGIN_LAUNCH();
+  hipLaunchKernelGGL(conv_halo_bilinear_kernel, grid, dim3(256), lds, s, b, hp);
+  return xpt_launch_status();
+}
+
 int dispatch_igemm(const ConvArgs& a, hipStream_t s) {
   const int classes = a.xs * a.xs;
   // pixels of the largest residue class
@@ -874,16 +1091,21 @@ extern "C" int xpt_conv2d_fwd(const void* x, const void* w, const float* bias, v
   if (B <= 0 || PH <= 0 || PW <= 0 || C <= 0 || N <= 0 || KH <= 0 || KW <= 0 || OH <= 0 || OW <= 0) return XPT_ERR_SHAPE;
   if (C % 8 != 0 || xpitch < C || xpitch % 8 != 0 || ypitch < N || ((uintptr_t)x) % 16 != 0 || ((uintptr_t)w) % 16 != 0)
     return XPT_ERR_ARG;
-  if (stride < 1 || (upsample != 0 && upsample != 1) || pad_t < 0 || pad_l < 0) return XPT_ERR_ARG;
+  if (stride < 1 || upsample < 0 || upsample > 2 || pad_t < 0 || pad_l < 0) return XPT_ERR_ARG;
+  // 2 = bilinear-2x input: 3 x 3, stride 1, SAME on the up-sampled map
+  if (upsample == 2 && (KH != 3 || KW != 3 || stride != 1 || pad_t != 1 || pad_l != 1 || OH != 2 * PH || OW != 2 * PW))
+    return XPT_ERR_ARG;
+  const int shift = upsample == 1 ? 1 : 0, grow = upsample ? 1 : 0;
   ConvArgs a{};
   a.x = (const unsigned short*)x; a.w = (const unsigned short*)w; a.bias = bias; a.y = (unsigned short*)y;
   a.xpitch = xpitch; a.ypitch = ypitch;
-  a.B = B; a.PH = PH; a.PW = PW; a.shift = upsample; a.Hlim = PH << upsample; a.Wlim = PW << upsample;
+  a.B = B; a.PH = PH; a.PW = PW; a.shift = shift; a.Hlim = PH << grow; a.Wlim = PW << grow;
   a.C = C; a.N = N; a.KH = KH; a.KW = KW;
   a.so = stride; a.sgn = 1; a.off_h = -pad_t; a.off_w = -pad_l;
   a.OH = OH; a.OW = OW; a.xs = 1; a.quad = 0; a.slope = slope;
   // the last window must start inside the padded input
   if ((long long)(OH - 1) * stride - pad_t >= a.Hlim || (long long)(OW - 1) * stride - pad_l >= a.Wlim) return XPT_ERR_SHAPE;
+  if (upsample == 2) return launch_halo_bilinear(a, (hipStream_t)stream);
   return dispatch_igemm(a, (hipStream_t)stream);
 }
 
@@ -908,6 +1130,22 @@ extern "C" int xpt_conv2d_bwd_data(const void* g, const void* wb, void* dx, int 
   a.OH = fold2x2 ? 2 * IH : IH; a.OW = fold2x2 ? 2 * IW : IW;
   a.xs = stride; a.quad = fold2x2; a.slope = 1.f;
   return dispatch_igemm(a, (hipStream_t)stream);
+}
+
+/* adjoint of the bilinear-2x operand load: gu [B,2 IH,2 IW,C] (pixel pitch gpitch) -> dx [B,IH,IW,C] (pixel pitch dxpitch) */
+extern "C" int xpt_bilinear2x_adjoint(const void* gu, long long gpitch, void* dx, long long dxpitch, int B, int IH, int IW,
+                                      int C, void* stream) {
+  XPT_CHECK_PTR(gu); XPT_CHECK_PTR(dx);
+  if (B <= 0 || IH <= 0 || IW <= 0 || C <= 0) return XPT_ERR_SHAPE;
+  if (C % 8 != 0 || gpitch < C || gpitch % 8 != 0 || dxpitch < C || dxpitch % 8 != 0 || ((uintptr_t)gu) % 16 != 0 ||
+      ((uintptr_t)dx) % 16 != 0)
+    return XPT_ERR_ARG;
+  const long long total = (long long)B * IH * IW * (C / 8);
+  if (total >= 0x7fffffffLL || IH >= (1 << 23) || IW >= (1 << 23)) return XPT_ERR_SHAPE;
+  XPT_BEGIN_LAUNCH();
+  hipLaunchKernelGGL(bilinear2x_adjoint_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const unsigned short*)gu, gpitch, (unsigned short*)dx, dxpitch, IH, IW, C / 8, total);
+  return xpt_launch_status();
 }
 
 extern "C" int xpt_conv_pack_job_bytes(void) { return (int)sizeof(PackJob); }

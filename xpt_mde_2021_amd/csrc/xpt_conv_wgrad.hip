@@ -96,8 +96,33 @@ __device__ __forceinline__ void wgrad_chunks(const WgradArgs& a, int tid, int n0
   }
 }
 
+// bilinear-2x operand load (the mode of the forward's halo-tile kernel, xpt_conv.hip): taps and weights of
+// at::upsample_bilinear2d(align_corners=False) at an exact factor 2, evaluated in fp32, rounded once to the 16-bit format
+__device__ __forceinline__ void wg_bil_taps(int y, int n, int& i0, int& i1, float& l) {
+  const float src = fmaxf(0.5f * (float)y - 0.25f, 0.f);
+  i0 = (int)src;
+  i1 = i0 + 1 < n ? i0 + 1 : n - 1;
+  l = src - (float)i0;
+}
+
+__device__ __forceinline__ u32x4 wg_bil_lerp8(const u32x4& a00, const u32x4& a01, const u32x4& a10, const u32x4& a11, float lh,
+                                              float lw) {
+  const float mh = 1.f - lh, mw = 1.f - lw;
+  u32x4 o;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float lo = mh * (mw * xpt_h2f_lo(a00[k]) + lw * xpt_h2f_lo(a01[k])) + lh * (mw * xpt_h2f_lo(a10[k]) + lw * xpt_h2f_lo(a11[k]));
+    const float hi = mh * (mw * xpt_h2f_hi(a00[k]) + lw * xpt_h2f_hi(a01[k])) + lh * (mw * xpt_h2f_hi(a10[k]) + lw * xpt_h2f_hi(a11[k]));
+    o[k] = (unsigned)xpt_f2h(lo) | ((unsigned)xpt_f2h(hi) << 16);
+  }
+  return o;
+}
+
 // the 16-byte chunks of one unit's g tile and x halo tile into registers
-template <int MAXCH>
+// (BIL: a.Hlim x a.Wlim = 2 PH x 2 PW is the up-sampled map the taps index, a.shift is not used; a chunk of the x halo is
+//  interpolated from its four physical neighbours as it is fetched -- four loads through the same descriptor, whose range
+//  check still supplies the zeros of the padding and of the dead chunks)
+template <int MAXCH, bool BIL = false>
 __device__ __forceinline__ void wgrad_fetch(const WgradArgs& a, int u, int gi, const WgradChunks<MAXCH>& w,
                                             const __amdgpu_buffer_rsrc_t& rg, const __amdgpu_buffer_rsrc_t& rx, u32x4 (&stage)[MAXCH]) {
   unsigned seg, rb;
@@ -117,8 +142,24 @@ __device__ __forceinline__ void wgrad_fetch(const WgradArgs& a, int u, int gi, c
     } else {
       const int r = th0 + w.row[i], c = tw0 + w.col[i];
       const bool ok = r >= 0 && c >= 0 && r < a.Hlim && c < a.Wlim;
-      const unsigned off = ok ? (ximg + (unsigned)((r >> a.shift) * a.PW + (c >> a.shift))) * xp2 + w.chb[i] : WG_OOB;
-      stage[i] = __builtin_amdgcn_raw_buffer_load_b128(rx, off, 0, 0);
+      if constexpr (BIL) {
+        int r0, r1, q0, q1;
+        float fh, fw;
+        wg_bil_taps(ok ? r : 0, a.PH, r0, r1, fh);
+        wg_bil_taps(ok ? c : 0, a.PW, q0, q1, fw);
+        const unsigned o00 = ok ? (ximg + (unsigned)(r0 * a.PW + q0)) * xp2 + w.chb[i] : WG_OOB;
+        const unsigned o01 = ok ? (ximg + (unsigned)(r0 * a.PW + q1)) * xp2 + w.chb[i] : WG_OOB;
+        const unsigned o10 = ok ? (ximg + (unsigned)(r1 * a.PW + q0)) * xp2 + w.chb[i] : WG_OOB;
+        const unsigned o11 = ok ? (ximg + (unsigned)(r1 * a.PW + q1)) * xp2 + w.chb[i] : WG_OOB;
+        const u32x4 a00 = __builtin_amdgcn_raw_buffer_load_b128(rx, o00, 0, 0);
+        const u32x4 a01 = __builtin_amdgcn_raw_buffer_load_b128(rx, o01, 0, 0);
+        const u32x4 a10 = __builtin_amdgcn_raw_buffer_load_b128(rx, o10, 0, 0);
+        const u32x4 a11 = __builtin_amdgcn_raw_buffer_load_b128(rx, o11, 0, 0);
+        stage[i] = wg_bil_lerp8(a00, a01, a10, a11, fh, fw);
+      } else {
+        const unsigned off = ok ? (ximg + (unsigned)((r >> a.shift) * a.PW + (c >> a.shift))) * xp2 + w.chb[i] : WG_OOB;
+        stage[i] = __builtin_amdgcn_raw_buffer_load_b128(rx, off, 0, 0);
+      }
     }
   }
 }
@@ -184,6 +225,103 @@ __global__ __launch_bounds__(256) void conv_wgrad_kernel(WgradArgs a) {
     __syncthreads();
     if (u + a.nsplit < a.units && !(a.dbg & 2))                // in flight during the products below
       wgrad_fetch<MAXCH>(a, u + a.nsplit, gi, chunks, rg, rx, stage);
+    if (active && !(a.dbg & 1)) {
+      for (int rr = 0; rr < a.R; ++rr) {
+        for (int c16 = 0; c16 < a.CB; c16 += 16) {
+          const unsigned ga = (unsigned)((rr * a.CB + c16) * TNB * 2);
+          const unsigned xa = (unsigned)(((rr * a.stride) * Wt + c16 * a.stride) * TCB * 2);
+          const bf16x8 fa = tr_pair(gs, a_base[0] + ga, a_base[1] + ga);
+#pragma unroll
+          for (int t = 0; t < TAPS; ++t) {
+            if (tap0 + t < T) {                                // wave-uniform
+              const bf16x8 fb = tr_pair(xs, b_base[0] + xa + toff[t], b_base[1] + xa + toff[t]);
+              acc[t] = XPT_MFMA_32X32X16(fa, fb, acc[t]);
+            }
+          }
+        }
+      }
+    }
+  }
+
+  // partial of this split: register e of tap t -> output channel n0 + 32 wn + (e & 3) + 8 (e >> 2) + 4 h,
+  // input channel c0 + 32 wc + (lane & 31)
+  if (!active || (a.dbg & 4)) return;
+  const int c = c0 + wc * 32 + (lane & 31);
+  float* dst = a.part + (long long)blockIdx.y * a.N * T * a.Cr;
+#pragma unroll
+  for (int t = 0; t < TAPS; ++t) {
+    if (tap0 + t >= T) continue;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const int n = n0 + wn * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+      if (n < a.N && c < a.Cr) dst[((long long)n * T + tap0 + t) * a.Cr + c] = acc[t][e];
+    }
+  }
+}
+
+// conv_wgrad_kernel with the bilinear-2x operand load (wgrad_fetch<MAXCH, true>): the x halo tile in LDS is the interpolated,
+// once-rounded up-sampled map; everything behind the staging is the kernel above, kept apart so that its code does not change
+template <int TAPS>
+__global__ __launch_bounds__(256) void conv_wgrad_bilinear_kernel(WgradArgs a) {
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int TNB = 32 * a.WN, TCB = 32 * a.WC;
+  const int T = a.KH * a.KW;
+  const int ntc = (a.C + TCB - 1) / TCB;
+  const int n0 = (blockIdx.x / ntc) * TNB, c0 = (blockIdx.x % ntc) * TCB;
+  const int HR = (a.R - 1) * a.stride + a.KH, Wt = (a.CB - 1) * a.stride + a.KW;
+  const int gchunks = a.R * a.CB * (TNB / 8), xchunks = HR * Wt * (TCB / 8);
+  const int gi = (gchunks + 255) >> 8;                         // staging slots that hold g chunks (whole passes of 256)
+  char* gs = smem;                                             // [R][CB][TNB] bf16
+  char* xs = smem + (size_t)gi * 256 * 16;                     // [HR][Wt][TCB] bf16, behind the padded g passes
+
+  // this wave's sub-tile and taps
+  const int wt = wave % a.WT, wc = (wave / a.WT) % a.WC, wn = wave / (a.WT * a.WC);
+  const int tap0 = wt * TAPS;
+  const bool active = tap0 < T;                                // wave-uniform
+  // lane roles of the transposed reads
+  const int g4 = lane >> 4, li = lane & 15, q = li >> 2, p = li & 3, h = g4 >> 1, half = g4 & 1;
+  unsigned a_base[2], b_base[2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int pc = 8 * h + 4 * i + q;                          // pixel column of this lane's row, read i
+    a_base[i] = (unsigned)((pc * TNB + wn * 32 + 16 * half + 4 * p) * 2);
+    b_base[i] = (unsigned)((pc * a.stride * TCB + wc * 32 + 16 * half + 4 * p) * 2);
+  }
+  unsigned toff[TAPS];
+#pragma unroll
+  for (int t = 0; t < TAPS; ++t) {
+    const int tap = tap0 + t < T ? tap0 + t : 0;
+    toff[t] = (unsigned)(((tap / a.KW) * Wt + (tap % a.KW)) * TCB * 2);
+  }
+
+  f32x16 acc[TAPS];
+#pragma unroll
+  for (int t = 0; t < TAPS; ++t)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
+
+  // Staging is software-pipelined: the 16-byte chunks of unit u+1 are fetched into registers while unit u is being
+  // multiplied (the loads stay in flight across the MFMA loop), then written to LDS behind the barrier that retires
+  // unit u's reads.  MAXCH chunks per thread bound the tile (the plan keeps gchunks + xchunks <= 256 * MAXCH).
+  constexpr int MAXCH = WGRAD_MAXCH;
+  const __amdgpu_buffer_rsrc_t rg = __builtin_amdgcn_make_buffer_rsrc((void*)a.g, 0, (int)a.gbytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, (int)a.xbytes, 0x00020000);
+  u32x4 stage[MAXCH];
+  WgradChunks<MAXCH> chunks;
+  wgrad_chunks<MAXCH>(a, tid, n0, c0, TNB, TCB, Wt, gi, gchunks, xchunks, chunks);
+  int u = blockIdx.y;
+  if (u < a.units) wgrad_fetch<MAXCH, true>(a, u, gi, chunks, rg, rx, stage);
+  for (; u < a.units; u += a.nsplit) {
+    __syncthreads();                                           // the previous unit's LDS reads are done
+#pragma unroll
+    for (int i = 0; i < MAXCH; ++i) {
+      const int ck = tid + 256 * i;                            // slot order = LDS order (g passes padded to 256 chunks)
+      if (i < gi ? ck < gchunks : ck - gi * 256 < xchunks) *(u32x4*)(smem + (size_t)ck * 16) = stage[i];
+    }
+    __syncthreads();
+    if (u + a.nsplit < a.units && !(a.dbg & 2))                // in flight during the products below
+      wgrad_fetch<MAXCH, true>(a, u + a.nsplit, gi, chunks, rg, rx, stage);
     if (active && !(a.dbg & 1)) {
       for (int rr = 0; rr < a.R; ++rr) {
         for (int c16 = 0; c16 < a.CB; c16 += 16) {
@@ -526,6 +664,17 @@ extern "C" int xpt_conv2d_bwd_weight_splits(int B, int C, int N, int KH, int KW,
   return p.nsplit;
 }
 
+/* splits of xpt_conv2d_bwd_weight_partials for a given operand-load mode (0 direct / 1 nearest-2x: the value of
+ * xpt_conv2d_bwd_weight_splits; 2 bilinear-2x: the general kernel's plan, the only family that serves it) */
+extern "C" int xpt_conv2d_bwd_weight_splits_mode(int B, int C, int N, int KH, int KW, int stride, int OH, int OW, int upsample) {
+  if (upsample != 2) return upsample == 0 || upsample == 1 ? xpt_conv2d_bwd_weight_splits(B, C, N, KH, KW, stride, OH, OW)
+                                                          : XPT_ERR_ARG;
+  if (B <= 0 || C <= 0 || N <= 0 || KH != 3 || KW != 3 || stride != 1 || OH <= 0 || OW <= 0) return XPT_ERR_SHAPE;
+  WgradPlan p;
+  if (!make_plan(B, C, N, KH, KW, stride, OH, OW, p)) return XPT_ERR_ARG;
+  return p.nsplit;
+}
+
 /* partials [splits][N][KH][KW][Cr] fp32 of dW = sum_m g[m][n] x[pixel(m,kh,kw)][c]; x has PH x PW physical pixels (the
  * taps index its nearest-2x up-sampling when upsample = 1) of C readable channels (multiple of 8) of which the first Cr
  * are real weight channels; g has N channels (multiple of 8). */
@@ -537,9 +686,12 @@ extern "C" int xpt_conv2d_bwd_weight_partials(const void* g, const void* x, floa
   if (B <= 0 || PH <= 0 || PW <= 0 || C <= 0 || Cr <= 0 || Cr > C || N <= 0 || KH <= 0 || KW <= 0 || OH <= 0 || OW <= 0)
     return XPT_ERR_SHAPE;
   if (C % 8 != 0 || N % 8 != 0 || xpitch < C || xpitch % 8 != 0 || gpitch < N || gpitch % 8 != 0 ||
-      ((uintptr_t)g) % 16 != 0 || ((uintptr_t)x) % 16 != 0 || stride < 1 || (upsample != 0 && upsample != 1))
+      ((uintptr_t)g) % 16 != 0 || ((uintptr_t)x) % 16 != 0 || stride < 1 || upsample < 0 || upsample > 2)
     return XPT_ERR_ARG;
-  {
+  // 2 = bilinear-2x input: 3 x 3, stride 1, SAME on the up-sampled map; served by the general kernel only
+  if (upsample == 2 && (KH != 3 || KW != 3 || stride != 1 || pad_t != 1 || pad_l != 1 || OH != 2 * PH || OW != 2 * PW))
+    return XPT_ERR_ARG;
+  if (upsample != 2) {
     WfArgs f{};
     if (fast_plan(B, C, N, KH, KW, stride, OH, OW, upsample, f) &&
         (upsample ? ((long long)PH * 2 == OH && (long long)PW * 2 == OW && pad_t == 1 && pad_l == 1)
@@ -572,7 +724,7 @@ extern "C" int xpt_conv2d_bwd_weight_partials(const void* g, const void* x, floa
   a.gbytes = ((long long)B * OH * OW - 1) * gpitch * 2 + (long long)N * 2;
   a.xbytes = ((long long)B * PH * PW - 1) * xpitch * 2 + (long long)C * 2;
   if (a.gbytes >= (1LL << 30) || a.xbytes >= (1LL << 30)) return XPT_ERR_SHAPE;      // 32-bit offsets + the 1 GiB out-of-range marker
-  a.B = B; a.PH = PH; a.PW = PW; a.shift = upsample; a.Hlim = PH << upsample; a.Wlim = PW << upsample;
+  a.B = B; a.PH = PH; a.PW = PW; a.shift = upsample == 1 ? 1 : 0; a.Hlim = PH << (upsample ? 1 : 0); a.Wlim = PW << (upsample ? 1 : 0);
   a.C = C; a.Cr = Cr; a.N = N; a.KH = KH; a.KW = KW; a.stride = stride; a.pad_t = pad_t; a.pad_l = pad_l;
   a.OH = OH; a.OW = OW;
   a.R = p.R; a.CB = p.CB; a.nseg = p.nseg; a.nrb = p.nrb; a.units = p.units; a.nsplit = p.nsplit;
@@ -582,6 +734,15 @@ extern "C" int xpt_conv2d_bwd_weight_partials(const void* g, const void* x, floa
   const dim3 grid(((N + TNB - 1) / TNB) * ((C + TCB - 1) / TCB), p.nsplit);
   hipStream_t s = (hipStream_t)stream;
   XPT_BEGIN_LAUNCH();
+  if (upsample == 2) {
+    switch (p.TAPS) {                                            // (a 3 x 3 filter: 9, 5 or 3 taps per wave)
+      case 3: hipLaunchKernelGGL(conv_wgrad_bilinear_kernel<3>, grid, dim3(256), p.lds, s, a); break;
+      case 5: hipLaunchKernelGGL(conv_wgrad_bilinear_kernel<5>, grid, dim3(256), p.lds, s, a); break;
+      case 9: hipLaunchKernelGGL(conv_wgrad_bilinear_kernel<9>, grid, dim3(256), p.lds, s, a); break;
+      default: return XPT_ERR_ARG;
+    }
+    return xpt_launch_status();
+  }
 #define XPT_WGRAD_CASE(TP)                                                                                         \
   case TP: {                                                                                                       \
     hipLaunchKernelGGL(conv_wgrad_kernel<TP>, grid, dim3(256), p.lds, s, a);                                       \

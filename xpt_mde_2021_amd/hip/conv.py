@@ -171,11 +171,26 @@ def nhwc_view(t, channels=None):
     return t, sw
 
 
+def upsample_mode(upsample):
+    """False / True / "nearest" / "bilinear" (or the kernels' 0 / 1 / 2) -> the `upsample` argument of the C entry points."""
+    if isinstance(upsample, str):
+        if upsample not in ("nearest", "bilinear"):
+            raise _lib.XptHipError(f"conv: unknown up-sampling mode {upsample!r} (nearest | bilinear)")
+        return 1 if upsample == "nearest" else 2
+    if isinstance(upsample, bool) or upsample in (0, 1, 2):
+        return int(upsample)
+    raise _lib.XptHipError(f"conv: unknown up-sampling mode {upsample!r}")
+
+
 _tuned = False
 
 
 class _Conv2dSame(torch.autograd.Function):
-    """y = LeakyReLU_slope(conv2d_same(x [nearest-2x up-sampled], weight, stride) + bias)."""
+    """y = LeakyReLU_slope(conv2d_same(x [nearest- or bilinear-2x up-sampled], weight, stride) + bias).
+    upsample: 0 direct, 1 nearest-2x, 2 bilinear-2x (3 x 3 stride-1 SAME layers; half-pixel centres, edge clamp, the operand
+    evaluated in fp32 and rounded once).  Mode 2 runs on the families that have it: forward = the halo-tile kernel of
+    xpt_conv2d_fwd, weight gradient = the general kernel, data gradient = the mode-0 data gradient of the up-sampled map into a
+    scratch tensor + ONE adjoint launch (xpt_bilinear2x_adjoint).  Only the low-resolution input is saved."""
 
     @staticmethod
     def forward(ctx, x, weight, bias, stride, slope, upsample, valid, pad):
@@ -191,7 +206,10 @@ class _Conv2dSame(torch.autograd.Function):
         N, C, KH, KW, Cp = e["N"], e["C"], e["KH"], e["KW"], e["Cp"]
         if Cx != Cp:
             raise _lib.XptHipError(f"conv: input has {Cx} channels, the packed weight expects {Cp} (= {C} padded to 8)")
-        H, W = PH << upsample, PW << upsample
+        grow = 1 if upsample else 0
+        H, W = PH << grow, PW << grow
+        if upsample == 2 and (KH != 3 or KW != 3 or stride != 1 or valid or pad >= 0):
+            raise _lib.XptHipError("conv: bilinear up-sampling is fused into 3 x 3 stride-1 SAME convolutions only")
         if pad >= 0:                                # ZeroPadding2D(pad) + padding="valid" (keras resnet_v2: conv1_pad, <name>_2_pad)
             if valid or 2 * pad > KH - 1 or 2 * pad > KW - 1:
                 raise _lib.XptHipError(f"conv: explicit padding {pad} with a {KH} x {KW} filter (valid={valid})")
@@ -210,8 +228,13 @@ class _Conv2dSame(torch.autograd.Function):
         b_ = None if bias is None else bias.detach()
         if b_ is not None and (b_.dtype != torch.float32 or not b_.is_contiguous()):
             raise _lib.XptHipError("conv: bias must be a contiguous float32 vector")
-        wsf = 0 if valid else lib.xpt_conv2d_splitk_workspace_floats(B * OH * OW, N, Cp, KH * KW, stride)
-        if wsf:
+        wsf = 0 if (valid or upsample == 2) else lib.xpt_conv2d_splitk_workspace_floats(B * OH * OW, N, Cp, KH * KW, stride)
+        if upsample == 2:
+            # bilinear-2x input: the split-K and persistent families do not have the mode; the general entry point does
+            _lib.check(lib.xpt_conv2d_fwd(x.data_ptr(), e["fwd"].data_ptr(), None if b_ is None else b_.data_ptr(),
+                                          y.data_ptr(), B, PH, PW, Cp, xpitch, N, KH, KW, stride, pt, pl, OH, OW, N,
+                                          2, float(slope), _stream()), "xpt_conv2d_fwd")
+        elif wsf:
             # deep layers on the small maps: LDS-tiled implicit GEMM with a deterministic split of the reduction axis
             ws = torch.empty(wsf, dtype=torch.float32, device=x.device)
             _lib.check(lib.xpt_conv2d_fwd_splitk(x.data_ptr(), e["fwd"].data_ptr(), None if b_ is None else b_.data_ptr(),
@@ -299,19 +322,28 @@ class _Conv2dSame(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             e = packer.get(weight, need_bwd=True)
             dx = torch.empty((B, Cp, PH, PW), dtype=_lib.half(), device=g.device, memory_format=torch.channels_last)
-            wsf = lib.xpt_conv2d_splitk_workspace_floats(B * (PH << ups) * (PW << ups), Cp, e["Np"], KH * KW, stride)
+            if ups == 2:
+                # bilinear: the plain (mode-0) data gradient w.r.t. the up-sampled map, then the interpolation's adjoint
+                IH, IW, fold = 2 * PH, 2 * PW, 0
+                dst = torch.empty((B, Cp, IH, IW), dtype=_lib.half(), device=g.device, memory_format=torch.channels_last)
+            else:
+                IH, IW, fold, dst = PH, PW, ups, dx
+            wsf = lib.xpt_conv2d_splitk_workspace_floats(B * (IH << fold) * (IW << fold), Cp, e["Np"], KH * KW, stride)
             if wsf:
                 ws = torch.empty(wsf, dtype=torch.float32, device=g.device)
-                _lib.check(lib.xpt_conv2d_bwd_data_splitk(g.data_ptr(), e["bwd"].data_ptr(), dx.data_ptr(), B, OH, OW, e["Np"],
-                                                          gpitch, Cp, KH, KW, pt, pl, PH, PW, Cp, ups, ws.data_ptr(), wsf,
+                _lib.check(lib.xpt_conv2d_bwd_data_splitk(g.data_ptr(), e["bwd"].data_ptr(), dst.data_ptr(), B, OH, OW, e["Np"],
+                                                          gpitch, Cp, KH, KW, pt, pl, IH, IW, Cp, fold, ws.data_ptr(), wsf,
                                                           _stream()), "xpt_conv2d_bwd_data_splitk")
-            elif KH == 3 and lib.xpt_conv2d_stream_serves(B, PH << ups, PW << ups, Cp, e["Np"], KH, KW, stride, ups):
-                _lib.check(lib.xpt_conv2d_bwd_data_stream(g.data_ptr(), e["bwd"].data_ptr(), dx.data_ptr(), B, OH, OW, e["Np"],
-                                                          gpitch, Cp, pt, pl, PH, PW, Cp, ups, _stream()),
+            elif KH == 3 and lib.xpt_conv2d_stream_serves(B, IH << fold, IW << fold, Cp, e["Np"], KH, KW, stride, fold):
+                _lib.check(lib.xpt_conv2d_bwd_data_stream(g.data_ptr(), e["bwd"].data_ptr(), dst.data_ptr(), B, OH, OW, e["Np"],
+                                                          gpitch, Cp, pt, pl, IH, IW, Cp, fold, _stream()),
                            "xpt_conv2d_bwd_data_stream")
             else:
-                _lib.check(lib.xpt_conv2d_bwd_data(g.data_ptr(), e["bwd"].data_ptr(), dx.data_ptr(), B, OH, OW, e["Np"], gpitch,
-                                                   Cp, KH, KW, stride, pt, pl, PH, PW, Cp, ups, _stream()), "xpt_conv2d_bwd_data")
+                _lib.check(lib.xpt_conv2d_bwd_data(g.data_ptr(), e["bwd"].data_ptr(), dst.data_ptr(), B, OH, OW, e["Np"], gpitch,
+                                                   Cp, KH, KW, stride, pt, pl, IH, IW, Cp, fold, _stream()), "xpt_conv2d_bwd_data")
+            if ups == 2:
+                _lib.check(lib.xpt_bilinear2x_adjoint(dst.data_ptr(), Cp, dx.data_ptr(), Cp, B, PH, PW, Cp, _stream()),
+                           "xpt_bilinear2x_adjoint")
         if _deferred and getattr(weight, "flush_wgrads", False):
             _flush_deferred(True)
         return dx, dw, dbias, None, None, None, None, None
@@ -359,7 +391,10 @@ def _wgrad_side_stream(device):
 
 def _weight_grad(ctx, lib, g, gpitch, x):
     B, PH, PW, Cp, C, xpitch, N, KH, KW, stride, pt, pl, OH, OW, ups, slope = ctx.geom
-    nsplit = lib.xpt_conv2d_bwd_weight_splits(B, Cp, N, KH, KW, stride, OH, OW)
+    if ups == 2:        # (the general kernel's plan: the specialised 3 x 3 kernel does not have the bilinear mode)
+        nsplit = lib.xpt_conv2d_bwd_weight_splits_mode(B, Cp, N, KH, KW, stride, OH, OW, ups)
+    else:
+        nsplit = lib.xpt_conv2d_bwd_weight_splits(B, Cp, N, KH, KW, stride, OH, OW)
     if nsplit < 1:
         raise _lib.XptHipError(f"xpt_conv2d_bwd_weight_splits failed: {nsplit}")
     n = N * KH * KW * C
@@ -384,10 +419,12 @@ def _weight_grad(ctx, lib, g, gpitch, x):
 def conv2d_same(x, weight, bias, stride=1, slope=1.0, upsample=False, valid=False, pad=None):
     """x [B,Cp,H,W] bf16 (NCHW-indexed, NHWC-stored; Cp = weight's input channels rounded up to 8, pad channels zero),
     weight [N,C,KH,KW] float32 master, bias [N] float32 or None -> [B,N,ceil(2^u H / stride),ceil(2^u W / stride)] bf16.
+    upsample: False | True / "nearest" | "bilinear" (u = 1 for both): x is read through UpSampling2D(2, interpolation).
     pad = p (an int, 2 p <= k - 1): `p` zeros on EVERY side and then a VALID convolution instead of TF SAME -- keras
     ZeroPadding2D(p) + Conv2D(padding="valid"), output (H + 2 p - k) // stride + 1; forward, data and weight gradient read the
     padding as out-of-range taps (no F.pad launch).  On an even extent at stride 2 this is NOT SAME, which pads (0, 1)."""
-    return _Conv2dSame.apply(x, weight, bias, int(stride), float(slope), bool(upsample), bool(valid), -1 if pad is None else int(pad))
+    return _Conv2dSame.apply(x, weight, bias, int(stride), float(slope), upsample_mode(upsample), bool(valid),
+                             -1 if pad is None else int(pad))
 
 
 def usable(x, conv, slope):

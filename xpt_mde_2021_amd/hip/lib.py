@@ -150,6 +150,8 @@ SIGNATURES = {
     "xpt_upsample2x_bwd_add": (_i, [_p, ctypes.c_longlong, _p, _p, ctypes.c_longlong, _i, _i, _i, _p]),
     "xpt_depth_head_ms_fwd": (_i, [_i, _p, _p, _p, _p, _p]),
     "xpt_depth_head_ms_bwd": (_i, [_i, _p, _p, _p, _p, _p, _p]),
+    "xpt_depth_head_exp_ms_fwd": (_i, [_i, _p, _p, _p, _p, _p]),
+    "xpt_depth_head_exp_ms_bwd": (_i, [_i, _p, _p, _p, _p, _p, _p]),
     "xpt_sum_rows": (_i, [_p, _p, _i, _p, ctypes.c_longlong, _i, _i, _p]),
     "xpt_photo_fused_ms_fwd": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _z, _i, _i, _p, _p, _p, _p]),   # losses is one [2 n, B] buffer
     "xpt_photo_fused_ms_bwd": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _z, _i, _i, _p, _p, _p, _p]),
@@ -200,6 +202,8 @@ SIGNATURES = {
                                         _i, _p]),
     "xpt_conv2d_bwd_weight_tune": (_i, [_i, _i]),
     "xpt_conv2d_bwd_weight_splits": (_i, [_i] * 8),
+    "xpt_conv2d_bwd_weight_splits_mode": (_i, [_i] * 9),
+    "xpt_bilinear2x_adjoint": (_i, [_p, ctypes.c_longlong, _p, ctypes.c_longlong, _i, _i, _i, _i, _p]),
     "xpt_conv2d_bwd_weight_partials": (_i, [_p, _p, _p, _z, _i, _i, _i, _i, _i, ctypes.c_longlong, _i, ctypes.c_longlong,
                                             _i, _i, _i, _i, _i, _i, _i, _i, _p]),
     "xpt_headconv_bwd_blocks": (_i, [_i, _i, _i, _i]),

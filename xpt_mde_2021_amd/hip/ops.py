@@ -1557,17 +1557,21 @@ class _DepthHeadMS(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, *xs):
+        return _DepthHeadMS.launch_forward(ctx, "xpt_depth_head_ms_fwd", "xpt_depth_head_ms_bwd", xs)
+
+    @staticmethod
+    def launch_forward(ctx, ctx_fwd, ctx_bwd, xs):
         import ctypes
         lib = _lib.load()
         ctx.set_materialize_grads(False)
         xs = [_dev(x, "x") for x in xs]
         n = len(xs)
+        ctx.bwd_name = ctx_bwd
         depths, disps = [torch.empty_like(x) for x in xs], [torch.empty_like(x) for x in xs]
         P = ctypes.c_void_p * n
         ptrs = lambda ts: P(*[t.data_ptr() for t in ts])       # noqa: E731
-        _lib.check(lib.xpt_depth_head_ms_fwd(n, ptrs(xs), ptrs(depths), ptrs(disps),
-                                             (ctypes.c_longlong * n)(*[x.numel() for x in xs]), _stream()),
-                   "xpt_depth_head_ms_fwd")
+        _lib.check(getattr(lib, ctx_fwd)(n, ptrs(xs), ptrs(depths), ptrs(disps),
+                                         (ctypes.c_longlong * n)(*[x.numel() for x in xs]), _stream()), ctx_fwd)
         ctx.save_for_backward(*xs)
         return (*depths, *disps)
 
@@ -1583,10 +1587,17 @@ class _DepthHeadMS(torch.autograd.Function):
         gxs = [torch.empty_like(x) for x in xs]
         P = ctypes.c_void_p * n
         ptrs = lambda ts: P(*[None if t is None else t.data_ptr() for t in ts])       # noqa: E731
-        _lib.check(lib.xpt_depth_head_ms_bwd(n, ptrs(xs), ptrs(gs[:n]), ptrs(gs[n:]), ptrs(gxs),
-                                             (ctypes.c_longlong * n)(*[x.numel() for x in xs]), _stream()),
-                   "xpt_depth_head_ms_bwd")
+        _lib.check(getattr(lib, ctx.bwd_name)(n, ptrs(xs), ptrs(gs[:n]), ptrs(gs[n:]), ptrs(gxs),
+                                              (ctypes.c_longlong * n)(*[x.numel() for x in xs]), _stream()), ctx.bwd_name)
         return tuple(gxs)
+
+
+class _DepthHeadExpMS(_DepthHeadMS):
+    """ExponentialActivation (model_factory.py:111-115) in the same two launches: depth = exp(10 sigmoid(x + 1) - 5)."""
+
+    @staticmethod
+    def forward(ctx, *xs):
+        return _DepthHeadMS.launch_forward(ctx, "xpt_depth_head_exp_ms_fwd", "xpt_depth_head_exp_ms_bwd", xs)
 
 
 def inverse_sigmoid_depth_multi(xs):
@@ -1594,6 +1605,55 @@ def inverse_sigmoid_depth_multi(xs):
     n = len(xs)
     out = _DepthHeadMS.apply(*xs)
     return list(out[:n]), list(out[n:])
+
+
+def exponential_depth_multi(xs):
+    """([depth_s], [disp_s]) = (exp(10 sigmoid(x_s + 1) - 5), safe_rcp(depth_s)) for up to 4 float32 prediction maps in one
+    launch (one more for the backward)."""
+    n = len(xs)
+    out = _DepthHeadExpMS.apply(*xs)
+    return list(out[:n]), list(out[n:])
+
+
+def exponential_depth(x):
+    """(depth, disp) of exponential_depth_multi for one map."""
+    depths, disps = exponential_depth_multi([x])
+    return depths[0], disps[0]
+
+
+def upsample2x_bilinear_torch(x):
+    """Pure-torch twin of the convolutions' bilinear-2x operand load (hip/conv.py, upsample="bilinear"): per axis
+    out[2i] = 0.25 in[max(i-1, 0)] + 0.75 in[i], out[2i+1] = 0.75 in[i] + 0.25 in[min(i+1, n-1)] (half-pixel centres, edge
+    clamp) on [..., H, W] -> [..., 2H, 2W]; equals F.interpolate(scale_factor=2, mode="bilinear", align_corners=False)."""
+    def axis(t, dim):
+        n = t.shape[dim]
+        idx = torch.arange(n, device=t.device)
+        prev, nxt = t.index_select(dim, (idx - 1).clamp(min=0)), t.index_select(dim, (idx + 1).clamp(max=n - 1))
+        even, odd = 0.25 * prev + 0.75 * t, 0.75 * t + 0.25 * nxt
+        shape = list(t.shape)
+        shape[dim] = 2 * n
+        return torch.stack([even, odd], dim=dim + 1 if dim >= 0 else dim).reshape(shape)
+    return axis(axis(x, x.dim() - 2), x.dim() - 1)
+
+
+def upsample2x_bilinear_adjoint_torch(g):
+    """Adjoint of upsample2x_bilinear_torch (the formula of csrc/xpt_conv.hip bilinear2x_adjoint_kernel): per axis input i
+    gathers 0.25 g[2i-1] + 0.75 g[2i] + 0.75 g[2i+1] + 0.25 g[2i+2], where the two border outputs g[0] and g[2n-1] count 1.0
+    (their clamped tap fell onto the border pixel itself) and taps outside [0, 2n) do not exist.  [..., 2H, 2W] -> [..., H, W]."""
+    def axis(t, dim):
+        m = t.shape[dim]
+        n = m // 2
+        w = torch.tensor([0.25, 0.75, 0.75, 0.25], dtype=t.dtype, device=t.device)
+        out = 0
+        for d in range(4):
+            pos = 2 * torch.arange(n, device=t.device) - 1 + d
+            live = (pos >= 0) & (pos < m)
+            wd = torch.where((pos == 0) | (pos == m - 1), torch.ones((), dtype=t.dtype, device=t.device), w[d]) * live.to(t.dtype)
+            shape = [1] * t.dim()
+            shape[dim] = n
+            out = out + t.index_select(dim, pos.clamp(0, m - 1)) * wd.view(shape)
+        return out
+    return axis(axis(g, g.dim() - 2), g.dim() - 1)
 
 
 def inverse_sigmoid_depth(x):

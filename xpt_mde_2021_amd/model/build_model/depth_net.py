@@ -32,11 +32,12 @@ class _ChannelsLastOne(torch.autograd.Function):
 
 _FUSED_CONCAT = __import__("os").environ.get("XPT_DEBUG_TORCH_CAT", "0") != "1"     # A/B: torch.cat + cached zero pad
 _FUSED_FAN_IN = __import__("os").environ.get("XPT_DEBUG_ATEN_FAN_IN", "0") != "1"    # A/B: autograd's add launches for the decoder's fan-ins
+_FUSED_BILINEAR = __import__("os").environ.get("XPT_DEBUG_ATEN_BILINEAR", "0") != "1"  # A/B: F.interpolate in front of conv1 ("bilinear")
 
 
 class UpconvWithSkip(nn.Module):
     """upconv_with_skip_connection of DepthNetNoResize (depth_net.py:101-109):
-    nearest 2x -> conv3x3 -> concat([., skip][, up-sampled previous prediction]) -> conv3x3."""
+    2x up-sampling (nearest | bilinear) -> conv3x3 -> concat([., skip][, up-sampled previous prediction]) -> conv3x3."""
 
     def __init__(self, conv2d, cin, skip_channels, out_channels, upsample_interp="nearest"):
         super().__init__()
@@ -47,7 +48,10 @@ class UpconvWithSkip(nn.Module):
     def forward(self, bef_layer, skips):
         if self.interp == "nearest":
             up = self.conv1(bef_layer, upsample=True)                             # UpSampling2D(2, "nearest") fused into the conv
-        else:
+        elif (_FUSED_BILINEAR and bef_layer.is_cuda and bef_layer.dtype == _half()
+              and _conv.usable(bef_layer, self.conv1.conv, self.conv1.slope) and self._fused_bilinear_wins(bef_layer)):
+            up = self.conv1(bef_layer, upsample="bilinear")                       # UpSampling2D(2, "bilinear") as the conv's operand load
+        else:                                                                     # host tensors, fp32 / fp64: the framework's resize
             up = self.conv1(F.interpolate(bef_layer, scale_factor=2, mode="bilinear", align_corners=False))
         parts = [up] + [s.to(up.dtype) for s in skips]
         if up.is_cuda and up.dtype == _half() and len(parts) <= 4 and _FUSED_CONCAT:
@@ -62,6 +66,14 @@ class UpconvWithSkip(nn.Module):
             # the matrix-core convolution reads 8-channel groups: the concatenation is built with its zero pad channels
             parts.append(self._zeros(up, -total % 8))
         return self.conv2(torch.cat(parts, dim=1))
+
+    @staticmethod
+    def _fused_bilinear_wins(x):
+        """Measured per layer (tools/bench_conv.py --upsample bilinear, batch 8): the fused mode wins on
+        up3 .. up0 (2 - 10x) and loses on up4.conv1 at the bench shape (1,056 -> 256 on 8 x 26: 270 against 227 us -- the
+        halo-tile forward walks 33 channel chunks of one round trip each), so a layer that deep AND that large keeps the
+        framework's resize; the small maps of the unit-test shapes stay fused."""
+        return x.shape[1] <= 256 or x.shape[0] * 4 * x.shape[2] * x.shape[3] < 1024
 
     def _zeros(self, like, channels):
         key = (like.shape[0], channels, like.shape[2], like.shape[3], like.device)

@@ -113,3 +113,19 @@ class ExponentialActivation:
 
     def __call__(self, x):
         return torch.exp(torch.sigmoid(x + 1.) * 10. - 5.)
+
+    def with_disparity(self, x):
+        """(depth, disp = safe_reciprocal_number(depth)): one gfx950 launch on the GPU (InverseSigmoidActivation's contract)."""
+        if x.is_cuda and x.dtype == torch.float32:
+            from ...hip import ops as _ops
+            return _ops.exponential_depth(x)
+        depth = self(x)
+        return depth, uf.safe_reciprocal_number(depth)
+
+    def with_disparity_multi(self, xs):
+        """with_disparity for every prediction scale of the decoder at once: ([depth_s], [disp_s])."""
+        if len(xs) <= 4 and all(x.is_cuda and x.dtype == torch.float32 for x in xs):
+            from ...hip import ops as _ops
+            return _ops.exponential_depth_multi(list(xs))
+        pairs = [self.with_disparity(x) for x in xs]
+        return [p[0] for p in pairs], [p[1] for p in pairs]

@@ -184,8 +184,9 @@ class Conv2DSame(nn.Module):
             nn.init.zeros_(self.conv.bias)
 
     def forward(self, x, upsample=False):
-        """`upsample`: the input is consumed through UpSampling2D(2, "nearest") (depth_net.py:76-84); on the matrix-core
-        path the up-sampled tensor is never materialised."""
+        """`upsample` (False / True / "nearest" / "bilinear"): the input is consumed through UpSampling2D(2, interpolation)
+        (depth_net.py:71-84; True = "nearest"); on the matrix-core path the up-sampled tensor is never materialised."""
+        upsample = _conv.upsample_mode(upsample)
         if _conv.usable(x, self.conv, self.slope):
             # gfx950 implicit-GEMM kernels (hip/conv.py): TF-SAME padding, bias, activation (and the up-sampling) fused;
             # no library call, so nothing in a captured training step depends on MIOpen's solvers or workspaces
@@ -195,7 +196,9 @@ class Conv2DSame(nn.Module):
             if x.shape[1] < cp:
                 x = F.pad(x, (0, 0, 0, 0, 0, cp - x.shape[1]))
             return _conv.conv2d_same(x, self.conv.weight, self.conv.bias, self.s, self.slope, upsample)
-        if upsample:
+        if upsample == 2:
+            x = F.interpolate(x, scale_factor=2, mode="bilinear", align_corners=False)
+        elif upsample:
             x = F.interpolate(x, scale_factor=2, mode="nearest")
         ph = same_pad(x.shape[2], self.k, self.s, self.d)
         pw = same_pad(x.shape[3], self.k, self.s, self.d)
