@@ -437,6 +437,20 @@ int xpt_conv2d_bwd_weight_splits_mode(int B, int C, int N, int KH, int KW, int s
 int xpt_bilinear2x_adjoint(const void* gu, long long gpitch, void* dx, long long dxpitch, int B, int IH, int IW, int C,
                            void* stream);
 
+/* ------------------------------------------------------------------ bilinear resize to an arbitrary size (csrc/xpt_resize.hip)
+ * resize_like / resize_image (model/model_util/layer_ops.py:39-50; tf.image.resize bilinear of TF2: half-pixel centres, no
+ * antialiasing, source coordinate (dst + 0.5) in / out - 0.5 clamped to the edges) on 16-bit NHWC feature maps, as
+ * DepthNetBasic puts it into every decoder level (model/build_model/depth_net.py:79).
+ * fwd: x [B,IH,IW,C] -> y [B,OH,OW,C]; interpolated in fp32, rounded once.
+ * adjoint: g [B,OH,OW,C] -> dx [B,IH,IW,C], the exact transpose in gather form (every input pixel sums the output pixels
+ *   that read it, fp32, fixed order, rounded once; no atomics).
+ * C % 8 == 0; pixel pitches in elements (>= C, multiples of 8: channel slices of wider tensors are read / written in place);
+ * 16-byte aligned pointers. */
+int xpt_resize_bilinear_fwd(const void* x, long long xpitch, void* y, long long ypitch, int B, int IH, int IW, int OH, int OW,
+                            int C, void* stream);
+int xpt_resize_bilinear_adjoint(const void* g, long long gpitch, void* dx, long long dxpitch, int B, int IH, int IW, int OH,
+                                int OW, int C, void* stream);
+
 /* ------------------------------------------------------------------ a2: decoder prediction heads
  * replaces the Conv2D(1, 3, padding="same", activation linear) of get_scaled_depth (model/build_model/depth_net.py:87-92)
  * and its tape.gradient: pre [B,H,W] fp32 = bias + conv3x3_same(x [B,H,W,C] bf16 with pixel pitch xpitch, w [3][3][C] fp32),

@@ -3,7 +3,9 @@
 (one GPU, batch 8, snippets 5 x 128 x 416, bf16, graph mode, synthetic data -- the trainer
 is built the way bench.py builds it).  bench.py measures the flagship (NASNet-Mobile) and is not edited for this.
 
-    python tools/bench_backbone.py [MobileNetV2|EfficientNetB0|ResNet50V2|NASNetMobile] [--steps 200] [--warmup 20]
+    python tools/bench_backbone.py [MobileNetV2|EfficientNetB0|ResNet50V2|NASNetMobile|DepthNetBasic] [--steps 200] [--warmup 20]
+
+(any name depth_net_factory builds; DepthNetNoResize needs --height / --width that are multiples of 128)
 
 Prints one JSON line; with XPT_BENCH_DW=1 also the device time of every depthwise-stage launch (replayed back to back from a
 captured graph, as tools/hot_replay.py does) against its algorithmic bytes at 8 TB/s; with XPT_BENCH_JUNCTION=1 (ResNet50V2) the

@@ -429,12 +429,14 @@ def conv2d_same(x, weight, bias, stride=1, slope=1.0, upsample=False, valid=Fals
 
 def usable(x, conv, slope):
     """Can this Conv2DSame call run on the matrix-core kernels?  (bf16 activations on the GPU, dense, undilated, at most
-    13 taps per wave group: k <= 5; heads with a single output channel go through their own kernels.)"""
+    13 taps per wave of the weight gradient: k <= 7 -- 7 x 7 = DepthNetBasic's dp_conv0b / dp_conv1a: forward and data gradient
+    on the general implicit-GEMM kernels, which take any filter extent, the weight gradient on the 13-tap instantiation that the
+    ResNet50V2 stem brought; heads with a single output channel go through their own kernels.)"""
     if not x.is_cuda or slope is None or conv.groups != 1 or conv.dilation != (1, 1):
         return False
     dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else x.dtype
     k = conv.kernel_size
-    return dtype == _lib.half() and k[0] == k[1] and k[0] in (1, 3, 5) and conv.out_channels % 8 == 0 \
+    return dtype == _lib.half() and k[0] == k[1] and k[0] in (1, 3, 5, 7) and conv.out_channels % 8 == 0 \
         and conv.weight.dtype == torch.float32
 
 

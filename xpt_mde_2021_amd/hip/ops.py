@@ -1551,6 +1551,63 @@ def upsample2x(x, dtype=torch.float32):
     return _Upsample2x.apply(x, dtype)
 
 
+def _half_pixels(t, what):
+    """NCHW-indexed 16-bit device tensor -> (tensor, pixel pitch in elements) for the 16-byte channel-vector kernels: dense
+    channels_last tensors and channel slices of them in place, anything else after a channels_last copy."""
+    if not t.is_cuda or t.dtype != _lib.half() or t.dim() != 4:
+        raise _lib.XptHipError(f"{what}: expected a 4-D {_lib.half()} CUDA/HIP tensor (no CPU fallback)")
+    B, C, H, W = t.shape
+    if C % 8 != 0:
+        raise _lib.XptHipError(f"{what}: {C} channels are not a multiple of 8")
+    sb, sc, sh, sw = t.stride()
+    if (sc == 1 and sh == W * sw and sb == H * sh and sw >= C and sw % 8 == 0 and t.data_ptr() % 16 == 0
+            and B * H * W > 1):
+        return t, sw
+    return t.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2), C
+
+
+def resize_bilinear_adjoint(g, size):
+    """Exact adjoint of resize_bilinear: g [B,C,oh,ow] (the gradient at the resized map) -> [B,C,ih,iw], size = (ih, iw)."""
+    lib = _lib.load()
+    ih, iw = int(size[0]), int(size[1])
+    g, gpitch = _half_pixels(g, "resize_bilinear_adjoint")
+    B, C, oh, ow = g.shape
+    dx = torch.empty((B, ih, iw, C), dtype=g.dtype, device=g.device).permute(0, 3, 1, 2)
+    _lib.check(lib.xpt_resize_bilinear_adjoint(_ptr(g), gpitch, _ptr(dx), C, B, ih, iw, oh, ow, C, _stream()),
+               "xpt_resize_bilinear_adjoint")
+    return dx
+
+
+class _ResizeBilinear(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, oh, ow):
+        lib = _lib.load()
+        x, xpitch = _half_pixels(x, "resize_bilinear")
+        B, C, ih, iw = x.shape
+        y = torch.empty((B, oh, ow, C), dtype=x.dtype, device=x.device).permute(0, 3, 1, 2)
+        _lib.check(lib.xpt_resize_bilinear_fwd(_ptr(x), xpitch, _ptr(y), C, B, ih, iw, oh, ow, C, _stream()),
+                   "xpt_resize_bilinear_fwd")
+        ctx.size = (ih, iw)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        return resize_bilinear_adjoint(g.to(_lib.half()), ctx.size), None, None
+
+
+def resize_bilinear(x, size):
+    """tf.image.resize(method="bilinear") of TF2 (half-pixel centres, no antialiasing, edge clamp; the numbers of
+    F.interpolate(align_corners=False, antialias=False)) of a 16-bit [B,C,h,w] map (NHWC storage, C a multiple of 8) to
+    size = (oh, ow), one gfx950 launch each way (csrc/xpt_resize.hip); equal sizes return x itself, like the reference's
+    resize_image (model/model_util/layer_ops.py:43-50)."""
+    oh, ow = int(size[0]), int(size[1])
+    if oh <= 0 or ow <= 0:
+        raise _lib.XptHipError(f"resize_bilinear: bad size {size!r}")
+    if (x.shape[2], x.shape[3]) == (oh, ow):
+        return x
+    return _ResizeBilinear.apply(x, oh, ow)
+
+
 class _DepthHeadMS(torch.autograd.Function):
     """The depth activation of every prediction scale in one launch (and one for the backward: the gradients of all
     scales come from the loss, so they are all there when the first decoder level is reached)."""

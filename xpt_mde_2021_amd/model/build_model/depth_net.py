@@ -1,5 +1,6 @@
 """DepthNetPretrained: multi-scale encoder + the reference's U-Net style decoder
-(model/build_model/depth_net.py:76-92 upsample / get_scaled_depth, :101-109 NoResize skip block, :137-167 decode).
+(model/build_model/depth_net.py:76-92 upsample / get_scaled_depth, :101-109 NoResize skip block, :137-167 decode);
+DepthNetBasic / DepthNetNoResize: the SfMLearner-style encoder-decoder without a backbone (:10-109).
 """
 import torch
 import torch.nn as nn
@@ -37,11 +38,14 @@ _FUSED_BILINEAR = __import__("os").environ.get("XPT_DEBUG_ATEN_BILINEAR", "0") !
 
 class UpconvWithSkip(nn.Module):
     """upconv_with_skip_connection of DepthNetNoResize (depth_net.py:101-109):
-    2x up-sampling (nearest | bilinear) -> conv3x3 -> concat([., skip][, up-sampled previous prediction]) -> conv3x3."""
+    2x up-sampling (nearest | bilinear) -> conv3x3 -> concat([., skip][, up-sampled previous prediction]) -> conv3x3.
+    resize=True: DepthNetBasic's block (depth_net.py:76-85), which resizes the first convolution's output to the skip's extent
+    (lo.resize_like) in front of the concatenation -- the identity wherever the encoder halved an even extent."""
 
-    def __init__(self, conv2d, cin, skip_channels, out_channels, upsample_interp="nearest"):
+    def __init__(self, conv2d, cin, skip_channels, out_channels, upsample_interp="nearest", resize=False):
         super().__init__()
         self.interp = upsample_interp
+        self.resize = resize
         self.conv1 = conv2d(cin, out_channels, 3)
         self.conv2 = conv2d(out_channels + skip_channels, out_channels, 3)
 
@@ -53,6 +57,8 @@ class UpconvWithSkip(nn.Module):
             up = self.conv1(bef_layer, upsample="bilinear")                       # UpSampling2D(2, "bilinear") as the conv's operand load
         else:                                                                     # host tensors, fp32 / fp64: the framework's resize
             up = self.conv1(F.interpolate(bef_layer, scale_factor=2, mode="bilinear", align_corners=False))
+        if self.resize:
+            up = lo.resize_like(up, skips[0])
         parts = [up] + [s.to(up.dtype) for s in skips]
         if up.is_cuda and up.dtype == _half() and len(parts) <= 4 and _FUSED_CONCAT:
             # the concatenation and its zero pad channels in one launch (torch.cat's batched copy ran at 0.5 - 0.8 TB/s here)
@@ -238,3 +244,137 @@ class DepthNetPretrained(nn.Module):
         if all(d is not None for d in disps):      # model_wrappers.py:48-49 would compute it with four more elementwise ops per scale
             out["disp_ms"] = [nhwc1(d) for d in disps]
         return out
+
+
+class DepthNetBasic(nn.Module):
+    """depth_net.py:10-92, the SfMLearner / GeoNet encoder-decoder (no pretrained backbone): fourteen convolutions down to 1/128
+    (7 x 7, 7 x 7, 5 x 5, 5 x 5, then 3 x 3; every second one at stride 2), seven decoder levels up6 .. up0 whose first
+    convolution's output is resized to the skip's extent (lo.resize_like: the encoder rounds odd extents UP, the 2x up-sampling
+    doubles them), prediction heads on up3 .. up0.
+    forward(image5d [B,S,H,W,3], already in [-1, 1]) -> {"depth_ms": [d0 (1/1), d1 (1/2), d2 (1/4), d3 (1/8)] each [B,h,w,1]
+    fp32, "disp_ms": likewise, "debug_out": [upconv0, upconv3]}.  The target frame is the LAST frame (:37).
+
+    Every layer is registered under the reference's layer name, the "_" between block and layer written as the module path's
+    ".": dp_conv0b, dp_up6.conv1 (= dp_up6_conv1), dp_depth3.conv (= dp_depth3_conv); layer_names() gives the mapping.
+    Kernel families at the bench shape: DESIGN.md section 13."""
+
+    RESIZE = True
+    # (name, filters, kernel, stride): depth_net.py:39-52
+    ENCODER = (("dp_conv0b", 32, 7, 1), ("dp_conv1a", 32, 7, 2), ("dp_conv1b", 64, 5, 1), ("dp_conv2a", 64, 5, 2),
+               ("dp_conv2b", 128, 3, 1), ("dp_conv3a", 128, 3, 2), ("dp_conv3b", 256, 3, 1), ("dp_conv4a", 256, 3, 2),
+               ("dp_conv4b", 512, 3, 1), ("dp_conv5a", 512, 3, 2), ("dp_conv5b", 512, 3, 1), ("dp_conv6a", 512, 3, 2),
+               ("dp_conv6b", 512, 3, 1), ("dp_conv7a", 512, 3, 2))
+    TAPS = ("dp_conv1b", "dp_conv2b", "dp_conv3b", "dp_conv4b", "dp_conv5b", "dp_conv6b", "dp_conv7a")     # conv1 .. conv7
+
+    def __init__(self, total_shape, global_batch, conv2d, pred_depth, upsample_iterp, high_res):
+        super().__init__()
+        self.total_shape = tuple(total_shape)
+        self.high_res = high_res
+        self.cut_backward = False      # DepthNetPretrained.forward: the cut sits between the encoder's taps and the decoder
+        self.cuts = []
+        cin = 3
+        for name, filters, k, s in self.ENCODER:
+            setattr(self, name, conv2d(cin, filters, k, strides=s))
+            cin = filters
+        up = lambda cin, skip, out: UpconvWithSkip(conv2d, cin, skip, out, upsample_iterp, resize=self.RESIZE)   # noqa: E731
+        self.dp_up6 = up(512, 512, 512)            # 1/64
+        self.dp_up5 = up(512, 512, 512)            # 1/32
+        self.dp_up4 = up(512, 512, 256)            # 1/16
+        self.dp_up3 = up(256, 256, 128)            # 1/8
+        self.dp_depth3 = ScaledDepthHead(conv2d, 128, pred_depth)
+        self.dp_up2 = up(128, 128 + 1, 64)         # 1/4
+        self.dp_depth2 = ScaledDepthHead(conv2d, 64, pred_depth)
+        self.dp_up1 = up(64, 64 + 1, 32)           # 1/2
+        self.dp_depth1 = ScaledDepthHead(conv2d, 32, pred_depth)
+        self.dp_up0 = up(32, 1, 16)                # 1/1: the "skip" is the up-sampled 1/2 prediction
+        self.dp_depth0 = ScaledDepthHead(conv2d, 16, pred_depth)
+
+    @property
+    def encoder(self):
+        """The fourteen encoder layers as one module (model_wrappers.set_backward_cut reads encoder.parameters()); a view, not
+        a registered child: the state dict keeps the flat layer names."""
+        return nn.ModuleList([getattr(self, name) for name, _, _, _ in self.ENCODER])
+
+    def layer_names(self):
+        """{reference layer name: its Conv2DSame}, in the reference's order of construction."""
+        out = {name: getattr(self, name) for name, _, _, _ in self.ENCODER}
+        for lvl in (6, 5, 4, 3):
+            out[f"dp_up{lvl}_conv1"], out[f"dp_up{lvl}_conv2"] = getattr(self, f"dp_up{lvl}").conv1, getattr(self, f"dp_up{lvl}").conv2
+        for lvl in (2, 1, 0):
+            out[f"dp_depth{lvl + 1}_conv"] = getattr(self, f"dp_depth{lvl + 1}").conv
+            out[f"dp_up{lvl}_conv1"], out[f"dp_up{lvl}_conv2"] = getattr(self, f"dp_up{lvl}").conv1, getattr(self, f"dp_up{lvl}").conv2
+        out["dp_depth0_conv"] = self.dp_depth0.conv
+        return out
+
+    def check_extent(self, height, width):
+        pass
+
+    def encode(self, image5d):
+        x = image5d[:, -1].permute(0, 3, 1, 2)                                    # [B,3,H,W] view of the NHWC frame
+        if image5d.dtype == torch.float32 and _conv.usable(x, self.dp_conv0b.conv, self.dp_conv0b.slope):
+            # the matrix-core path: the target frame cast to the 16-bit format with its five zero pad channels in one launch
+            x = _conv.restack_bf16(image5d[:, -1:], 8)
+        taps = []
+        for name, _, _, _ in self.ENCODER:
+            x = getattr(self, name)(x)
+            if name in self.TAPS:
+                taps.append(x)
+        return taps
+
+    def forward(self, image5d):
+        height, width = image5d.shape[2:4]
+        self.check_extent(height, width)
+        taps = self.encode(image5d)
+        if self.cut_backward and torch.is_grad_enabled() and all(t.requires_grad for t in taps):
+            leaves = [t.detach().requires_grad_(True) for t in taps]
+            self.cuts.append((taps, leaves))
+            taps = leaves
+        return self.decode(*taps, height, width)
+
+    def decode(self, conv1, conv2, conv3, conv4, conv5, conv6, conv7, height, width):
+        heads = (self.dp_depth0, self.dp_depth1, self.dp_depth2, self.dp_depth3)
+        batched = _BATCHED_HEADS and conv7.is_cuda and hasattr(self.dp_depth0.predict_depth, "with_disparity_multi")
+        upconv6 = self.dp_up6(conv7, [conv6])
+        upconv5 = self.dp_up5(upconv6, [conv5])
+        upconv4 = self.dp_up4(upconv5, [conv4])
+        upconv3 = self.dp_up3(upconv4, [conv3])
+        depth3, dpconv2_up, dpconv3, upconv3 = self.dp_depth3(upconv3, height // 4, width // 4, not batched, split=True)
+        upconv2 = self.dp_up2(upconv3, [conv2, dpconv2_up])
+        depth2, dpconv1_up, dpconv2, upconv2 = self.dp_depth2(upconv2, height // 2, width // 2, not batched, split=True)
+        upconv1 = self.dp_up1(upconv2, [conv1, dpconv1_up])
+        depth1, dpconv0_up, dpconv1, upconv1 = self.dp_depth1(upconv1, height, width, not batched, split=True)
+        upconv0 = self.dp_up0(upconv1, [dpconv0_up])
+        depth0, _, dpconv0 = self.dp_depth0(upconv0, height, width, not batched)
+        if batched:
+            with torch.autocast(device_type=conv7.device.type, enabled=False):
+                (depth0, depth1, depth2, depth3), disps = self.dp_depth0.predict_depth.with_disparity_multi(
+                    [dpconv0, dpconv1, dpconv2, dpconv3])
+            for h, d in zip(heads, disps):
+                h.last_disp = d
+
+        def nhwc1(x):      # [B,1,h,w] -> [B,h,w,1]: same memory, the reference's axis order
+            return x.contiguous().reshape(x.shape[0], x.shape[2], x.shape[3], 1)
+
+        out = {"depth_ms": [nhwc1(depth0), nhwc1(depth1), nhwc1(depth2), nhwc1(depth3)],
+               "debug_out": [upconv0, upconv3]}
+        disps = [h.last_disp for h in heads]
+        for h in heads:        # (DepthNetPretrained.decode: nothing of this step's graph stays on the module)
+            h.last_disp = None
+        if all(d is not None for d in disps):
+            out["disp_ms"] = [nhwc1(d) for d in disps]
+        return out
+
+
+class DepthNetNoResize(DepthNetBasic):
+    """depth_net.py:94-109: DepthNetBasic without the resize in its decoder levels.  Height and width must be multiples of 128
+    (the reference's graph does not build otherwise: the concatenation's operands differ in extent)."""
+
+    RESIZE = False
+
+    def __init__(self, total_shape, global_batch, conv2d, pred_depth, upsample_iterp, high_res):
+        super().__init__(total_shape, global_batch, conv2d, pred_depth, upsample_iterp, high_res)
+        self.check_extent(self.total_shape[2], self.total_shape[3])
+
+    def check_extent(self, height, width):
+        if height % 128 or width % 128:
+            raise WrongInputException(f"[DepthNetNoResize] height and width must be multiples of 128, got {height} x {width}")

@@ -69,6 +69,11 @@ class ModelFactory:
         if net_name in PRETRAINED_MODELS:
             return dn.DepthNetPretrained(self.bshwc_shape, self.global_batch, conv2d_d, pred_activ, upsample_interp,
                                          net_name, self.pretrained_weight, self.high_res)
+        if net_name == "DepthNetBasic":
+            return dn.DepthNetBasic(self.bshwc_shape, self.global_batch, conv2d_d, pred_activ, upsample_interp, self.high_res)
+        if net_name == "DepthNetNoResize":
+            return dn.DepthNetNoResize(self.bshwc_shape, self.global_batch, conv2d_d, pred_activ, upsample_interp,
+                                       self.high_res)
         raise WrongInputException("[depth_net_factory] depth net outside this build's hot path: " + net_name)
 
     def pose_net_factory(self, net_name, conv2d_p):

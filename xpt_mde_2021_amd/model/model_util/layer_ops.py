@@ -243,6 +243,10 @@ def resize_image(src, dst_height, dst_width):
     """layer_ops.py:43-50: TF2 bilinear resize (half-pixel centres) of NCHW `src`; identity if sizes match."""
     if src.shape[2] == dst_height and src.shape[3] == dst_width:
         return src
+    if src.is_cuda and src.dtype == _half() and src.shape[1] % 8 == 0:
+        # 16-bit feature maps on the GPU (DepthNetBasic's decoder levels): one gfx950 launch each way (csrc/xpt_resize.hip);
+        # host tensors, fp32 / fp64 and the one-channel predictions keep the framework's resize below
+        return _ops.resize_bilinear(src, (dst_height, dst_width))
     return F.interpolate(src, size=(dst_height, dst_width), mode="bilinear", align_corners=False, antialias=False)
 
 
