@@ -436,6 +436,30 @@ int xpt_restack_bf16(const float* image5d, void* out, int B, int S, int H, int W
 int xpt_conv2d_bwd_weight_splits_mode(int B, int C, int N, int KH, int KW, int stride, int OH, int OW, int upsample);
 int xpt_bilinear2x_adjoint(const void* gu, long long gpitch, void* dx, long long dxpitch, int B, int IH, int IW, int C,
                            void* stream);
+/* Dilated 3 x 3 convolutions (csrc/xpt_conv_dilated.hip; PWC-Net's context network, model/build_model/flow_net.py:
+ * Conv2D(3, padding="same", dilation_rate=d), d = 2, 4, 8, 16): stride 1, TF SAME = `dilation` zeros on every side, so input
+ * and output are both H x W.  Operands as above: NHWC 16-bit activations with a pixel pitch, the packer's fwd [N][9][Cp] /
+ * bwd [Cp][9][Np] weights, fp32 bias (may be NULL).  No workspace, no atomics, fixed summation order.
+ * xpt_conv2d_dilated_fwd: y[b,oh,ow,n] = act(bias[n] + sum_{kh,kw,c} x[b, oh + (kh-1) d, ow + (kw-1) d, c] w[n,kh,kw,c]),
+ *   zeros outside the map, act = LeakyReLU(slope) (1 = linear).  Taps out of range for a whole wave tile are not visited.
+ * xpt_conv2d_dilated_bwd_data: dx[b,ih,iw,c] = sum_{kh,kw,n} g[b, ih - (kh-1) d, iw - (kw-1) d, n] w[n,kh,kw,c] on the bwd
+ *   packing (no zero-stuffing, no flipped-weight copy, no scratch tensor); g has Np readable channels, dx gets C channels.
+ * xpt_conv2d_dilated_bwd_weight_partials: split-K partial sums [splits][N][3][3][Cr] fp32 of
+ *   dw[n,kh,kw,c] = sum_{b,oh,ow} g[b,oh,ow,n] x[b, oh + (kh-1) d, ow + (kw-1) d, c]  (c < Cr <= C), the layout of
+ *   xpt_conv2d_bwd_weight_partials; splits = xpt_conv2d_dilated_bwd_weight_splits(...) (>= 1, or an error code); finished
+ *   by xpt_reduce_partials.
+ * Every entry point returns XPT_ERR_ARG before any launch for dilation < 1, a filter that is not 3 x 3, a stride other than
+ * 1, channel counts that are not multiples of 8, NULL operand pointers, pitches / pointers that break the 16-byte fragment
+ * loads, and a partials buffer smaller than splits * N * 9 * Cr floats; XPT_ERR_SHAPE for non-positive extents. */
+int xpt_conv2d_dilated_fwd(const void* x, const void* w, const float* bias, void* y, int B, int H, int W, int C,
+                           long long xpitch, int N, int KH, int KW, int stride, int dilation, long long ypitch, float slope,
+                           void* stream);
+int xpt_conv2d_dilated_bwd_data(const void* g, const void* wb, void* dx, int B, int H, int W, int Np, long long gpitch,
+                                int C, int KH, int KW, int stride, int dilation, long long dxpitch, void* stream);
+int xpt_conv2d_dilated_bwd_weight_splits(int B, int C, int N, int KH, int KW, int stride, int dilation, int H, int W);
+int xpt_conv2d_dilated_bwd_weight_partials(const void* g, const void* x, float* partials, size_t partial_floats, int B,
+                                           int H, int W, int C, int Cr, long long xpitch, int N, long long gpitch, int KH,
+                                           int KW, int stride, int dilation, void* stream);
 
 /* ------------------------------------------------------------------ bilinear resize to an arbitrary size (csrc/xpt_resize.hip)
  * resize_like / resize_image (model/model_util/layer_ops.py:39-50; tf.image.resize bilinear of TF2: half-pixel centres, no

@@ -24,9 +24,10 @@ def round_up(n, m):
     return (n + m - 1) // m * m
 
 
-def same_pad(n, k, s):
-    """TF "SAME" (model/model_util/layer_ops.py padding="same"): total = max((ceil(n/s)-1)*s + k - n, 0); before = total // 2."""
-    total = max((math.ceil(n / s) - 1) * s + k - n, 0)
+def same_pad(n, k, s, d=1):
+    """TF "SAME" (model/model_util/layer_ops.py padding="same"): total = max((ceil(n/s)-1)*s + k_eff - n, 0) with
+    k_eff = (k - 1) d + 1; before = total // 2."""
+    total = max((math.ceil(n / s) - 1) * s + (k - 1) * d + 1 - n, 0)
     return total // 2, total - total // 2
 
 
@@ -190,10 +191,12 @@ class _Conv2dSame(torch.autograd.Function):
     upsample: 0 direct, 1 nearest-2x, 2 bilinear-2x (3 x 3 stride-1 SAME layers; half-pixel centres, edge clamp, the operand
     evaluated in fp32 and rounded once).  Mode 2 runs on the families that have it: forward = the halo-tile kernel of
     xpt_conv2d_fwd, weight gradient = the general kernel, data gradient = the mode-0 data gradient of the up-sampled map into a
-    scratch tensor + ONE adjoint launch (xpt_bilinear2x_adjoint).  Only the low-resolution input is saved."""
+    scratch tensor + ONE adjoint launch (xpt_bilinear2x_adjoint).  Only the low-resolution input is saved.
+    dilation > 1 (3 x 3, stride 1, SAME, no up-sampling: PWC-Net's context network): forward, data gradient and weight gradient
+    are the launches of csrc/xpt_conv_dilated.hip; everything around them in the backward is the shared code."""
 
     @staticmethod
-    def forward(ctx, x, weight, bias, stride, slope, upsample, valid, pad):
+    def forward(ctx, x, weight, bias, stride, slope, upsample, valid, pad, dilation=1):
         lib = _lib.load()
         global _tuned
         if not _tuned:
@@ -210,7 +213,16 @@ class _Conv2dSame(torch.autograd.Function):
         H, W = PH << grow, PW << grow
         if upsample == 2 and (KH != 3 or KW != 3 or stride != 1 or valid or pad >= 0):
             raise _lib.XptHipError("conv: bilinear up-sampling is fused into 3 x 3 stride-1 SAME convolutions only")
-        if pad >= 0:                                # ZeroPadding2D(pad) + padding="valid" (keras resnet_v2: conv1_pad, <name>_2_pad)
+        if dilation != 1:
+            if dilation < 1 or KH != 3 or KW != 3 or stride != 1 or upsample or valid or pad >= 0:
+                raise _lib.XptHipError(f"conv: dilation {dilation} is served for 3 x 3 stride-1 SAME convolutions without "
+                                       f"up-sampling only (got {KH} x {KW}, stride {stride}, upsample {upsample}, "
+                                       f"valid={valid}, pad={pad})")
+            if N % 8 != 0:
+                raise _lib.XptHipError(f"conv: dilated convolution with {N} output channels (not a multiple of 8)")
+            pt = pl = dilation                      # TF SAME at stride 1: (k - 1) d zeros in all, d on each side
+            OH, OW = H, W
+        elif pad >= 0:                              # ZeroPadding2D(pad) + padding="valid" (keras resnet_v2: conv1_pad, <name>_2_pad)
             if valid or 2 * pad > KH - 1 or 2 * pad > KW - 1:
                 raise _lib.XptHipError(f"conv: explicit padding {pad} with a {KH} x {KW} filter (valid={valid})")
             pt = pl = pad
@@ -228,8 +240,13 @@ class _Conv2dSame(torch.autograd.Function):
         b_ = None if bias is None else bias.detach()
         if b_ is not None and (b_.dtype != torch.float32 or not b_.is_contiguous()):
             raise _lib.XptHipError("conv: bias must be a contiguous float32 vector")
-        wsf = 0 if (valid or upsample == 2) else lib.xpt_conv2d_splitk_workspace_floats(B * OH * OW, N, Cp, KH * KW, stride)
-        if upsample == 2:
+        wsf = 0 if (valid or upsample == 2 or dilation != 1) else \
+            lib.xpt_conv2d_splitk_workspace_floats(B * OH * OW, N, Cp, KH * KW, stride)
+        if dilation != 1:
+            _lib.check(lib.xpt_conv2d_dilated_fwd(x.data_ptr(), e["fwd"].data_ptr(), None if b_ is None else b_.data_ptr(),
+                                                  y.data_ptr(), B, H, W, Cp, xpitch, N, KH, KW, stride, dilation, N,
+                                                  float(slope), _stream()), "xpt_conv2d_dilated_fwd")
+        elif upsample == 2:
             # bilinear-2x input: the split-K and persistent families do not have the mode; the general entry point does
             _lib.check(lib.xpt_conv2d_fwd(x.data_ptr(), e["fwd"].data_ptr(), None if b_ is None else b_.data_ptr(),
                                           y.data_ptr(), B, PH, PW, Cp, xpitch, N, KH, KW, stride, pt, pl, OH, OW, N,
@@ -257,6 +274,7 @@ class _Conv2dSame(torch.autograd.Function):
                                           int(upsample), float(slope), _stream()), "xpt_conv2d_fwd")
         ctx.save_for_backward(x, y if slope != 1.0 else None, b_)
         ctx.geom = (B, PH, PW, Cp, C, xpitch, N, KH, KW, stride, pt, pl, OH, OW, int(upsample), float(slope))
+        ctx.dilation = dilation
         ctx.weight = weight
         ctx.sink_w = weight.flat_grad if (_ops.grad_sink.wants(weight) and N % 8 == 0) else None
         ctx.sink_b = bias.flat_grad if (bias is not None and _ops.grad_sink.wants(bias)) else None
@@ -328,8 +346,13 @@ class _Conv2dSame(torch.autograd.Function):
                 dst = torch.empty((B, Cp, IH, IW), dtype=_lib.half(), device=g.device, memory_format=torch.channels_last)
             else:
                 IH, IW, fold, dst = PH, PW, ups, dx
-            wsf = lib.xpt_conv2d_splitk_workspace_floats(B * (IH << fold) * (IW << fold), Cp, e["Np"], KH * KW, stride)
-            if wsf:
+            wsf = 0 if ctx.dilation != 1 else \
+                lib.xpt_conv2d_splitk_workspace_floats(B * (IH << fold) * (IW << fold), Cp, e["Np"], KH * KW, stride)
+            if ctx.dilation != 1:
+                _lib.check(lib.xpt_conv2d_dilated_bwd_data(g.data_ptr(), e["bwd"].data_ptr(), dx.data_ptr(), B, PH, PW, e["Np"],
+                                                           gpitch, Cp, KH, KW, stride, ctx.dilation, Cp, _stream()),
+                           "xpt_conv2d_dilated_bwd_data")
+            elif wsf:
                 ws = torch.empty(wsf, dtype=torch.float32, device=g.device)
                 _lib.check(lib.xpt_conv2d_bwd_data_splitk(g.data_ptr(), e["bwd"].data_ptr(), dst.data_ptr(), B, OH, OW, e["Np"],
                                                           gpitch, Cp, KH, KW, pt, pl, IH, IW, Cp, fold, ws.data_ptr(), wsf,
@@ -346,7 +369,7 @@ class _Conv2dSame(torch.autograd.Function):
                            "xpt_bilinear2x_adjoint")
         if _deferred and getattr(weight, "flush_wgrads", False):
             _flush_deferred(True)
-        return dx, dw, dbias, None, None, None, None, None
+        return dx, dw, dbias, None, None, None, None, None, None
 
 
 # The decoder's weight gradients as ONE parallel branch of the step: a fork per layer costs more than it returns (below), so the
@@ -391,20 +414,28 @@ def _wgrad_side_stream(device):
 
 def _weight_grad(ctx, lib, g, gpitch, x):
     B, PH, PW, Cp, C, xpitch, N, KH, KW, stride, pt, pl, OH, OW, ups, slope = ctx.geom
-    if ups == 2:        # (the general kernel's plan: the specialised 3 x 3 kernel does not have the bilinear mode)
+    dil = ctx.dilation
+    if dil != 1:
+        nsplit = lib.xpt_conv2d_dilated_bwd_weight_splits(B, Cp, N, KH, KW, stride, dil, OH, OW)
+    elif ups == 2:      # (the general kernel's plan: the specialised 3 x 3 kernel does not have the bilinear mode)
         nsplit = lib.xpt_conv2d_bwd_weight_splits_mode(B, Cp, N, KH, KW, stride, OH, OW, ups)
     else:
         nsplit = lib.xpt_conv2d_bwd_weight_splits(B, Cp, N, KH, KW, stride, OH, OW)
     if nsplit < 1:
-        raise _lib.XptHipError(f"xpt_conv2d_bwd_weight_splits failed: {nsplit}")
+        raise _lib.XptHipError(f"xpt_conv2d{'_dilated' if dil != 1 else ''}_bwd_weight_splits failed: {nsplit}")
     n = N * KH * KW * C
     if ctx.sink_w is not None:
         ws = _ops.grad_sink.partials(ctx.sink_w, "convw", nsplit * n)
     else:
         ws = torch.empty(nsplit * n, dtype=torch.float32, device=g.device)
-    _lib.check(lib.xpt_conv2d_bwd_weight_partials(g.data_ptr(), x.data_ptr(), ws.data_ptr(), ws.numel(), B, PH, PW, Cp, C,
-                                                  xpitch, N, gpitch, KH, KW, stride, pt, pl, OH, OW, ups, _stream()),
-               "xpt_conv2d_bwd_weight_partials")
+    if dil != 1:
+        _lib.check(lib.xpt_conv2d_dilated_bwd_weight_partials(g.data_ptr(), x.data_ptr(), ws.data_ptr(), ws.numel(), B, PH, PW,
+                                                              Cp, C, xpitch, N, gpitch, KH, KW, stride, dil, _stream()),
+                   "xpt_conv2d_dilated_bwd_weight_partials")
+    else:
+        _lib.check(lib.xpt_conv2d_bwd_weight_partials(g.data_ptr(), x.data_ptr(), ws.data_ptr(), ws.numel(), B, PH, PW, Cp, C,
+                                                      xpitch, N, gpitch, KH, KW, stride, pt, pl, OH, OW, ups, _stream()),
+                   "xpt_conv2d_bwd_weight_partials")
     if ctx.sink_w is not None:
         _ops.grad_sink.add(ctx.sink_w, ws, 0, n, nsplit, n)
         return None
@@ -416,28 +447,59 @@ def _weight_grad(ctx, lib, g, gpitch, x):
     return ws[:nsplit * n].view(nsplit, N, KH, KW, C).sum(0).permute(0, 3, 1, 2)
 
 
-def conv2d_same(x, weight, bias, stride=1, slope=1.0, upsample=False, valid=False, pad=None):
+def conv2d_same(x, weight, bias, stride=1, slope=1.0, upsample=False, valid=False, pad=None, dilation=1):
     """x [B,Cp,H,W] bf16 (NCHW-indexed, NHWC-stored; Cp = weight's input channels rounded up to 8, pad channels zero),
     weight [N,C,KH,KW] float32 master, bias [N] float32 or None -> [B,N,ceil(2^u H / stride),ceil(2^u W / stride)] bf16.
     upsample: False | True / "nearest" | "bilinear" (u = 1 for both): x is read through UpSampling2D(2, interpolation).
     pad = p (an int, 2 p <= k - 1): `p` zeros on EVERY side and then a VALID convolution instead of TF SAME -- keras
     ZeroPadding2D(p) + Conv2D(padding="valid"), output (H + 2 p - k) // stride + 1; forward, data and weight gradient read the
-    padding as out-of-range taps (no F.pad launch).  On an even extent at stride 2 this is NOT SAME, which pads (0, 1)."""
-    return _Conv2dSame.apply(x, weight, bias, int(stride), float(slope), upsample_mode(upsample), bool(valid),
-                             -1 if pad is None else int(pad))
+    padding as out-of-range taps (no F.pad launch).  On an even extent at stride 2 this is NOT SAME, which pads (0, 1).
+    dilation = d > 1: Conv2D(3, padding="same", dilation_rate=d) on csrc/xpt_conv_dilated.hip -- 3 x 3, stride 1, SAME, no
+    up-sampling, output channels a multiple of 8; any other combination raises XptHipError (nothing falls through)."""
+    dilation = int(dilation)
+    if dilation < 1:
+        raise _lib.XptHipError(f"conv: dilation {dilation} < 1")
+    if dilation == 1:                               # exactly the undilated call
+        return _Conv2dSame.apply(x, weight, bias, int(stride), float(slope), upsample_mode(upsample), bool(valid),
+                                 -1 if pad is None else int(pad), 1)
+    ups = upsample_mode(upsample)
+    if tuple(weight.shape[2:]) != (3, 3) or int(stride) != 1 or ups or valid or pad is not None:
+        raise _lib.XptHipError(f"conv: dilation {dilation} is served for 3 x 3 stride-1 SAME convolutions without up-sampling "
+                               f"only (got a {tuple(weight.shape[2:])} filter, stride {stride}, upsample {upsample!r}, "
+                               f"valid={valid}, pad={pad})")
+    return _Conv2dSame.apply(x, weight, bias, 1, float(slope), 0, False, -1, dilation)
+
+
+# A/B switch: XPT_DEBUG_LIBRARY_DILATED=1 sends the dilated 3 x 3 layers (PWC-Net's context network) back through the library
+# path of layer_ops.conv2d_library, as before csrc/xpt_conv_dilated.hip
+LIBRARY_DILATED = __import__("os").environ.get("XPT_DEBUG_LIBRARY_DILATED", "0") == "1"
+
+
+def geometry_usable(kernel_size, stride, dilation, groups, out_channels, library_dilated=None):
+    """The shape half of usable() (pure Python: no tensor, no device): dense square filters with k in 1 / 3 / 5 / 7 and output
+    channels a multiple of 8; dilation (d, d) with d > 1 for 3 x 3 stride-1 layers only, and not under the A/B switch."""
+    if library_dilated is None:
+        library_dilated = LIBRARY_DILATED
+    k, s, d = tuple(kernel_size), tuple(stride), tuple(dilation)
+    if groups != 1 or k[0] != k[1] or k[0] not in (1, 3, 5, 7) or out_channels % 8 != 0:
+        return False
+    if d != (1, 1):
+        return d[0] == d[1] and d[0] > 1 and k == (3, 3) and s == (1, 1) and not library_dilated
+    return True
 
 
 def usable(x, conv, slope):
-    """Can this Conv2DSame call run on the matrix-core kernels?  (bf16 activations on the GPU, dense, undilated, at most
+    """Can this Conv2DSame call run on the matrix-core kernels?  (bf16 activations on the GPU, dense, at most
     13 taps per wave of the weight gradient: k <= 7 -- 7 x 7 = DepthNetBasic's dp_conv0b / dp_conv1a: forward and data gradient
     on the general implicit-GEMM kernels, which take any filter extent, the weight gradient on the 13-tap instantiation that the
-    ResNet50V2 stem brought; heads with a single output channel go through their own kernels.)"""
-    if not x.is_cuda or slope is None or conv.groups != 1 or conv.dilation != (1, 1):
+    ResNet50V2 stem brought; heads with a single output channel go through their own kernels.  Dilated: 3 x 3 stride 1,
+    csrc/xpt_conv_dilated.hip -- geometry_usable().)"""
+    if not x.is_cuda or slope is None:
+        return False
+    if not geometry_usable(conv.kernel_size, conv.stride, conv.dilation, conv.groups, conv.out_channels):
         return False
     dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled() else x.dtype
-    k = conv.kernel_size
-    return dtype == _lib.half() and k[0] == k[1] and k[0] in (1, 3, 5, 7) and conv.out_channels % 8 == 0 \
-        and conv.weight.dtype == torch.float32
+    return dtype == _lib.half() and conv.weight.dtype == torch.float32
 
 
 def stem_input_usable(image):

@@ -204,6 +204,13 @@ SIGNATURES = {
     "xpt_conv2d_bwd_weight_splits": (_i, [_i] * 8),
     "xpt_conv2d_bwd_weight_splits_mode": (_i, [_i] * 9),
     "xpt_bilinear2x_adjoint": (_i, [_p, ctypes.c_longlong, _p, ctypes.c_longlong, _i, _i, _i, _i, _p]),
+    "xpt_conv2d_dilated_fwd": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, ctypes.c_longlong, _i, _i, _i, _i, _i,
+                                    ctypes.c_longlong, _f, _p]),
+    "xpt_conv2d_dilated_bwd_data": (_i, [_p, _p, _p, _i, _i, _i, _i, ctypes.c_longlong, _i, _i, _i, _i, _i,
+                                         ctypes.c_longlong, _p]),
+    "xpt_conv2d_dilated_bwd_weight_splits": (_i, [_i] * 9),
+    "xpt_conv2d_dilated_bwd_weight_partials": (_i, [_p, _p, _p, _z, _i, _i, _i, _i, _i, ctypes.c_longlong, _i,
+                                                    ctypes.c_longlong, _i, _i, _i, _i, _p]),
     "xpt_resize_bilinear_fwd": (_i, [_p, ctypes.c_longlong, _p, ctypes.c_longlong, _i, _i, _i, _i, _i, _i, _p]),
     "xpt_resize_bilinear_adjoint": (_i, [_p, ctypes.c_longlong, _p, ctypes.c_longlong, _i, _i, _i, _i, _i, _i, _p]),
     "xpt_conv2d_bwd_weight_partials": (_i, [_p, _p, _p, _z, _i, _i, _i, _i, _i, ctypes.c_longlong, _i, ctypes.c_longlong,

@@ -11,7 +11,12 @@ as [batch, numsrc, H/2^p, W/2^p, 2].
 
 The cost volume is the gfx950 kernel pair of csrc/xpt_corr.hip (tfa.layers.CorrelationCost semantics); the feature warp
 follows tfa.image.dense_image_warp (bilinear, border-clamped, flow channel 0 = rows) through the library's grid sampler;
-convolutions go through the same Conv2DSame factory as PoseNet / the decoder (MIOpen, fp32 weight gradients).
+convolutions go through the same Conv2DSame factory as PoseNet / the decoder.  On the GPU under 16-bit autocast that means the
+library's own implicit-GEMM kernels (hip/conv.py) for every layer whose output channels are a multiple of 8 -- the encoders,
+the estimators' 128 / 96 / 64 / 32-wide layers, and the dilated 3 x 3 layers of the context network, context[1..4] (d = 2, 4, 8,
+16: csrc/xpt_conv_dilated.hip; XPT_DEBUG_LIBRARY_DILATED=1 puts those four back on the library path).  Still through MIOpen
+(layer_ops.conv2d_library, fp32 weight gradients): the 2-channel flow heads (32 -> 2), the 196-channel layers of encoder
+level 6 (196 is no multiple of 8) and the transposed up-samplers.
 """
 import torch
 import torch.nn as nn

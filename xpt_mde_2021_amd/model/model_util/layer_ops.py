@@ -195,7 +195,7 @@ class Conv2DSame(nn.Module):
                 x = x.to(_half())
             if x.shape[1] < cp:
                 x = F.pad(x, (0, 0, 0, 0, 0, cp - x.shape[1]))
-            return _conv.conv2d_same(x, self.conv.weight, self.conv.bias, self.s, self.slope, upsample)
+            return _conv.conv2d_same(x, self.conv.weight, self.conv.bias, self.s, self.slope, upsample, dilation=self.d)
         if upsample == 2:
             x = F.interpolate(x, scale_factor=2, mode="bilinear", align_corners=False)
         elif upsample:
