@@ -13,7 +13,8 @@ pytestmark = pytest.mark.gpu
 
 # every kernel family against its fp32 torch reference / the oracle, unchanged bars (half has three more mantissa bits than bf16)
 KERNEL_SUITES = ["tests/test_conv_igemm_gpu.py", "tests/test_cell_tail_gpu.py", "tests/test_grad_sink.py", "tests/test_hip_parity.py",
-                 "tests/test_adam_parity.py"]
+                 "tests/test_adam_parity.py",
+                 "tests/test_conv_exact_gpu.py"]     # exact-integer operands: equality, the same cases in the process's 16-bit format
 
 
 def _child(args, timeout, **env):
