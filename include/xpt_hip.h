@@ -492,6 +492,42 @@ int xpt_headconv_bwd_add(const void* x, long long xpitch, const float* w, const 
                          long long addend_pitch, void* dx, float* partials, size_t partial_floats, int B, int H, int W, int C,
                          void* stream);
 
+/* ------------------------------------------------------------------ PWC-Net's 2-channel layers (csrc/xpt_flowtail.hip)
+ * The flow heads, Conv2D(2, 3, "same", linear) (_FlowEstimator.out, context[6]), and the transposed up-samplers,
+ * Conv2DTranspose(2, 4, 2, "same") = conv_transpose2d(stride 2, padding 1) (up_flow 2 -> 2, up_feat 32 -> 2) of
+ * model/build_model/flow_net.py, as VALU kernels in the manner of the depth heads above: fp32 master weights read in their
+ * channels-last memory order, fp32 results, ONE backward launch per operator that writes dx and per-workgroup partial rows
+ * (dW in the weight's memory layout, then the two bias sums) for xpt_reduce_partials.  No workspace besides the partials, no
+ * atomics, fixed summation order, every output element written exactly once.
+ * xpt_flowhead_fwd: pre[b,oh,ow,n] = bias[n] + sum_{kh,kw,c} x[b, oh + kh - 1, ow + kw - 1, c] w[n,kh,kw,c], n in {0, 1}, zeros
+ *   outside the map.  x: 16-bit NHWC with pixel pitch xpitch, C in {16, 32, 64, 128}; w [2][3][3][C] fp32; bias [2] fp32 or
+ *   NULL; pre [B,H,W,2] fp32.
+ * xpt_flowhead_bwd: g [B,H,W,2] fp32 -> dx [B,H,W,C] 16-bit dense (rounded once) and partials
+ *   [xpt_flowhead_bwd_blocks()][18 C + 2] fp32 (dW [2][3][3][C], then db [2]).
+ * xpt_upconv4x4s2_fwd: y[b,oy,ox,n] = bias[n] + sum_{c,ky,kx : oy = 2 iy - 1 + ky, ox = 2 ix - 1 + kx} x[b,iy,ix,c] W[c,ky,kx,n],
+ *   evaluated per output phase (2 x 2 taps per output, nothing zero-stuffed).  x_fp32 = 1: x [B,H,W,2] fp32 contiguous
+ *   (xpitch = 2), C = 2; x_fp32 = 0: x 16-bit NHWC with pixel pitch xpitch, C in {8, 16, 32}.  W [C][4][4][2] fp32; bias [2]
+ *   fp32 or NULL; y [B,2H,2W,2] fp32.
+ * xpt_upconv4x4s2_bwd: g [B,2H,2W,2] fp32 -> dx [B,H,W,C] dense in x's own format,
+ *   dx[b,iy,ix,c] = sum_{n,ky,kx} g[b, 2 iy - 1 + ky, 2 ix - 1 + kx, n] W[c,ky,kx,n] (g outside the map reads as zero), and
+ *   partials [xpt_upconv4x4s2_bwd_blocks()][32 C + 2] fp32 (dW [C][4][4][2] = sum x g, then db [2] = sum g).
+ * The *_bwd_blocks functions return the number of partial rows (>= 1), or 0 for arguments the kernels do not serve.
+ * Every entry point returns before any launch: XPT_ERR_NULL for a NULL operand (bias excepted), XPT_ERR_SHAPE for non-positive
+ * extents, H or W of 2^24 or more, or 2^31 - 1 or more pixels (the up-sampler: output pixels), XPT_ERR_ARG for a channel count
+ * outside the sets above, an x_fp32 flag other than 0 / 1, a pitch below C or no multiple of 8 (fp32 input: other than 2) or a
+ * pointer that breaks the vector accesses (16 bytes: 16-bit x and dx, y; 8 bytes: fp32 x and dx, pre, g), XPT_ERR_WORKSPACE
+ * for a partials buffer smaller than blocks * row floats. */
+int xpt_flowhead_bwd_blocks(int B, int H, int W, int C);
+int xpt_flowhead_fwd(const void* x, long long xpitch, const float* w, const float* bias, float* pre, int B, int H, int W,
+                     int C, void* stream);
+int xpt_flowhead_bwd(const void* x, long long xpitch, const float* w, const float* g, void* dx, float* partials,
+                     size_t partial_floats, int B, int H, int W, int C, void* stream);
+int xpt_upconv4x4s2_bwd_blocks(int B, int H, int W, int C, int x_fp32);
+int xpt_upconv4x4s2_fwd(const void* x, long long xpitch, int x_fp32, const float* w, const float* bias, float* y, int B, int H,
+                        int W, int C, void* stream);
+int xpt_upconv4x4s2_bwd(const void* x, long long xpitch, int x_fp32, const float* w, const float* g, void* dx, float* partials,
+                        size_t partial_floats, int B, int H, int W, int C, void* stream);
+
 /* ------------------------------------------------------------------ a2/a4: depth head activation
  * InverseSigmoid (model/build_model/model_factory.py:134-138) and safe_reciprocal_number (utils/util_funcs.py:157-160):
  *   depth = safe_rcp(sigmoid(x) + 0.01), disp = safe_rcp(depth), safe_rcp(v) = (1 / v) [v > 1e-5]; float32, n elements.

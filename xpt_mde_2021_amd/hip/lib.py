@@ -219,6 +219,12 @@ SIGNATURES = {
     "xpt_headconv_fwd": (_i, [_p, ctypes.c_longlong, _p, _p, _p, _i, _i, _i, _i, _p]),
     "xpt_headconv_bwd": (_i, [_p, ctypes.c_longlong, _p, _p, _p, _p, _z, _i, _i, _i, _i, _p]),
     "xpt_headconv_bwd_add": (_i, [_p, ctypes.c_longlong, _p, _p, _p, ctypes.c_longlong, _p, _p, _z, _i, _i, _i, _i, _p]),
+    "xpt_flowhead_bwd_blocks": (_i, [_i, _i, _i, _i]),
+    "xpt_flowhead_fwd": (_i, [_p, ctypes.c_longlong, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "xpt_flowhead_bwd": (_i, [_p, ctypes.c_longlong, _p, _p, _p, _p, _z, _i, _i, _i, _i, _p]),
+    "xpt_upconv4x4s2_bwd_blocks": (_i, [_i, _i, _i, _i, _i]),
+    "xpt_upconv4x4s2_fwd": (_i, [_p, ctypes.c_longlong, _i, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "xpt_upconv4x4s2_bwd": (_i, [_p, ctypes.c_longlong, _i, _p, _p, _p, _p, _z, _i, _i, _i, _i, _p]),
     "xpt_restack_bf16": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
     "xpt_affine_act_fwd": (_i, [_p, _p, _p, _p, _p, _f, _p, _p, ctypes.c_longlong, _i, _f, _i, _i, _p]),
     "xpt_affine_act_bwd_workspace_floats": (_z, [ctypes.c_longlong, _i]),

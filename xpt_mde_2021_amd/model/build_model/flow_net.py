@@ -14,14 +14,20 @@ follows tfa.image.dense_image_warp (bilinear, border-clamped, flow channel 0 = r
 convolutions go through the same Conv2DSame factory as PoseNet / the decoder.  On the GPU under 16-bit autocast that means the
 library's own implicit-GEMM kernels (hip/conv.py) for every layer whose output channels are a multiple of 8 -- the encoders,
 the estimators' 128 / 96 / 64 / 32-wide layers, and the dilated 3 x 3 layers of the context network, context[1..4] (d = 2, 4, 8,
-16: csrc/xpt_conv_dilated.hip; XPT_DEBUG_LIBRARY_DILATED=1 puts those four back on the library path).  Still through MIOpen
-(layer_ops.conv2d_library, fp32 weight gradients): the 2-channel flow heads (32 -> 2), the 196-channel layers of encoder
-level 6 (196 is no multiple of 8) and the transposed up-samplers.
+16: csrc/xpt_conv_dilated.hip; XPT_DEBUG_LIBRARY_DILATED=1 puts those four back on the library path).  The fourteen 2-channel
+layers run on csrc/xpt_flowtail.hip (hip/flowtail.py), one launch forward and one backward each: the six linear flow heads
+(_FlowEstimator.out five times, context[6]; XPT_DEBUG_LIBRARY_FLOWHEAD=1 puts them back on the library path) and the eight
+transposed up-samplers (up_flow, up_feat on levels 6..3; XPT_DEBUG_LIBRARY_UPCONV=1).  They produce fp32, so the flow is fp32
+from its head through the up-sampler to the warp and to flow_ms.  Still through MIOpen (layer_ops.conv2d_library, fp32 weight
+gradients): the six 196-channel layers of encoder level 6 (196 is no multiple of 8).  On the CPU and in fp32 mode every layer
+takes the framework path it always took.
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ...hip import flowtail as _flowtail
+from ...hip import lib as _lib
 from ...hip import ops as _ops
 from ...utils.util_class import WrongInputException
 from ..model_util import layer_ops as lo
@@ -54,7 +60,17 @@ def dense_image_warp(image, flow):
     return out.to(image.dtype)
 
 
-_LIBRARY_UPCONV = __import__("os").environ.get("XPT_DEBUG_LIBRARY_UPCONV", "0") == "1"      # A/B switch
+# A/B switches, consulted at call time: 1 = the layers take the library path they took before csrc/xpt_flowtail.hip
+_LIBRARY_UPCONV = __import__("os").environ.get("XPT_DEBUG_LIBRARY_UPCONV", "0") == "1"
+_LIBRARY_FLOWHEAD = __import__("os").environ.get("XPT_DEBUG_LIBRARY_FLOWHEAD", "0") == "1"
+
+
+def _flow_head(layer, x):
+    """A Conv2DSame(32, 2, 3, activation="linear") flow head on x: the own kernel (fp32 flow from 16-bit features) on the GPU
+    under 16-bit autocast, else the layer itself."""
+    if not _LIBRARY_FLOWHEAD and layer.slope == 1.0 and _flowtail.flow_head_usable(x, layer.conv):
+        return _flowtail.flow_head(x if x.dtype == _lib.half() else x.to(_lib.half()), layer.conv.weight, layer.conv.bias)
+    return layer(x)
 
 
 class _UpConvFp32(torch.autograd.Function):
@@ -89,7 +105,14 @@ class _UpConv(nn.Module):
         nn.init.xavier_uniform_(self.weight)
 
     def forward(self, x):
+        if not _LIBRARY_UPCONV:
+            # (a 2-channel flow that a library head left in 16 bits is consumed as fp32, as the fp32 path below does)
+            xk = x.float() if (x.is_cuda and x.shape[1] == 2 and x.dtype != torch.float32) else x
+            if _flowtail.upconv_usable(xk, self.weight):
+                return _flowtail.upconv4x4s2(xk, self.weight, self.bias)
         with torch.autocast(device_type=x.device.type, enabled=False):
+            if _LIBRARY_UPCONV:
+                lo.note_library_conv(x)             # counted like every other library convolution of the step
             y = F.conv_transpose2d(x.float(), self.weight, None, 2, 1) if _LIBRARY_UPCONV else \
                 _UpConvFp32.apply(x.float(), self.weight)
             if y.is_cuda:
@@ -118,7 +141,7 @@ class _FlowEstimator(nn.Module):
         for conv in self.convs:
             x = torch.cat([x, conv(x)], dim=1)
         c = self.last(x)
-        flow = self.out(c)
+        flow = _flow_head(self.out, c)
         if self.up:
             return flow, self.up_flow(flow), self.up_feat(c)
         return flow, c
@@ -209,8 +232,9 @@ class PWCNet(nn.Module):
         flow2, flow_feat2 = self.upconv_flow(2, self.flow2, c2l, c2r, up_flow3, up_feat3)
 
         c = flow_feat2
-        for conv in self.context:
+        for conv in self.context[:-1]:
             c = conv(c)
+        c = _flow_head(self.context[-1], c)
         flow2 = c + flow2
         # reshape_batch_back (:101-110): [B*N, 2, h, w] -> [B, N, h, w, 2]
         flow_ms = [f.float().permute(0, 2, 3, 1).reshape(batch, numsrc, f.shape[2], f.shape[3], 2)
